@@ -194,6 +194,59 @@ def _replay_rate(det, bsz, a, D, replays=200, windows=5, step=None, make_det=Non
     return res
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000      # --dump-outputs: all arrays together (the .npy headers add < 1 kB each)
+
+
+# per-class work lists of the detector step: with top_k each class list stops as soon as its next pick cannot reach the image's
+# top-100 (ops.class_nms), a point that depends on which classes got there first, so their lengths vary from run to run; the
+# detections taken from them do not
+DUMP_SKIP = ('class_dets', 'class_counts')
+
+
+def dump_outputs(out, directory, budget=DUMP_BUDGET_BYTES, skip=()):
+    """Write every tensor of `out` (a step's result dict; nested dicts / lists are flattened to dotted names) as
+    `directory/<name>.npy`: floating tensors as float32 (float64 stays float64), integer and bool tensors as float64 (exact).
+    An array larger than its share of `budget` is replaced by a fixed sample of its flattened elements: indices drawn without
+    replacement by numpy's default_rng(0), sorted -- they depend only on the element count, so that two builds of the project
+    dump the same positions.  Names in `skip` are not written.  Returns {name: {'shape', 'dtype', 'elements_written', 'sampled'}}."""
+    import numpy as np
+    flat = []
+
+    def walk(prefix, v):
+        if prefix in skip:
+            return
+        if torch.is_tensor(v):
+            flat.append((prefix, v.detach()))
+        elif isinstance(v, dict):
+            for k in sorted(v):
+                walk('%s.%s' % (prefix, k) if prefix else str(k), v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk('%s.%d' % (prefix, i), x)
+    walk('', out)
+    os.makedirs(directory, exist_ok=True)
+    itemsize = lambda t: 8 if (t.dtype == torch.float64 or not t.is_floating_point()) else 4
+    # water-filling: the smallest arrays are written whole, the rest share what is left equally
+    flat.sort(key=lambda nt: nt[1].numel() * itemsize(nt[1]))
+    left, manifest = budget, {}
+    for i, (name, t) in enumerate(flat):
+        share = left // (len(flat) - i)
+        n = t.numel()
+        k = min(n, share // itemsize(t))
+        v = t.reshape(-1)
+        if k < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        v = v.to(torch.float32 if (t.is_floating_point() and t.dtype != torch.float64) else torch.float64).cpu().numpy()
+        if k == n:
+            v = v.reshape(tuple(t.shape))
+        np.save(os.path.join(directory, name + '.npy'), v)
+        left -= v.nbytes
+        manifest[name] = {'shape': list(t.shape), 'dtype': str(t.dtype).replace('torch.', ''), 'elements_written': int(k),
+                          'sampled': k < n}
+    return manifest
+
+
 def _side_figure(fn, what):
     """Run one SIDE figure of the default line (training rates, other configs).  An exception there -- out of memory, a collective
     error, a diverged 5-step random-init run -- is recorded as {'error': ...} under the figure's key instead of losing the headline
@@ -380,6 +433,9 @@ def bench_train(a, rank, world, D, emit=True, fatal=True):
             one_step()
         fence()
         elapsed = time.perf_counter() - t0
+        dumped = None
+        if emit and rank == 0 and getattr(a, 'dump_outputs', None):      # (outside the timed region)
+            dumped = dump_outputs({'step': out, 'weights_master': tr.W.master}, a.dump_outputs)
         comm = None
         if world > 1:       # self-diagnosis of the N > 1 line (verdict r05 item 8), OUTSIDE the timed region: the same steps again with HIP
             tr.comm_timing = []               # events around every bucket's wait -> exposed communication per step and per bucket
@@ -447,6 +503,8 @@ def bench_train(a, rank, world, D, emit=True, fatal=True):
             'communication': comm if comm is not None else 'single rank: no collective',
             'losses': {k: float(out[k]) for k in ('bbox_loss', 'rpn_bbox_loss', 'nms_pos_loss', 'nms_neg_loss') if k in out},
             'weights_finite_on_all_ranks': bool(ok)}
+        if dumped is not None:
+            res['outputs_dumped'] = {'dir': a.dump_outputs, 'arrays': dumped}
         if emit:
             print(json.dumps(res))
     del tr
@@ -486,7 +544,14 @@ def main():
                     help='std of the random cls_score / bbox_pred weights (reference init: 0.01, which makes every class posterior '
                          '~1/81 and the parity block blind to the head; the cost of the step does not depend on it)')
     ap.add_argument('--stub', action='store_true', help='launcher dry run: gloo ranks on CPU, a stub step instead of the detector')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's detector outputs; with --train "
+                         "the step's outputs and the updated fp32 master weights) as DIR/<name>.npy, float32 / float64, at most "
+                         "64 MB in all (a fixed sample of the larger arrays); the inputs are seeded, so two builds compare output "
+                         "for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
     if a.batch is None:
         # 108 images: 1010 row tiles of 256 on the res4 maps = 3.95 rounds over 256 CUs (54: 505 = 1.97 rounds) and half the per-launch
         # ramps per image: +2 % images/s over 54 on the same box (r04); the other graphs keep 54 (27 / 8 in other_configs)
@@ -599,6 +664,7 @@ def main():
                 out = step()
         fence()
         elapsed = time.perf_counter() - t0
+        dumped = dump_outputs(out, a.dump_outputs, skip=DUMP_SKIP) if (a.dump_outputs and rank == 0) else None   # (outside the timed region)
         # throughput mode (detector.InFlight), a SIDE figure of the line (`in_flight`): the same K steps with two batches in flight -- a second
         # detector instance (own buffers), a second resident batch, each step captured on its own stream, steps submitted round-robin.
         # `value` stays the one-at-a-time rate of rounds 1-5
@@ -674,6 +740,9 @@ def main():
                                          'single GPU; at N > 1 the data-parallel scaling figure is train.value (training step incl. the RCCL all-reduce)',
                        **({'one_device_test': 'all %d ranks share cuda:0 and exchange over gloo (RELNET_BENCH_ONE_DEVICE): a code-path check, NOT a multi-GPU number' % world} if one_dev else {})},
         }
+        if dumped is not None:
+            res['outputs_dumped'] = {'dir': a.dump_outputs, 'arrays': dumped,
+                                     'not_dumped': [k for k in DUMP_SKIP if k in out], 'why_not': 'run-dependent list lengths (ops.class_nms top_k)'}
         if flight_err is not None:
             res['in_flight'] = {'error': flight_err}
         if elapsed_fl is not None:

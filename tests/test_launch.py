@@ -90,3 +90,33 @@ def test_training_benchmark_lr_rule():
     assert bench.bench_lr(0.0005, 1, 1) == 0.0005 and bench.bench_lr(0.0005, 8, 1) == 0.0005 and bench.bench_lr(0.0005, 16, 1) == 0.0005
     assert bench.bench_lr(0.0005, 8, 4) == pytest.approx(0.00025) and bench.bench_lr(0.0005, 8, 8) == pytest.approx(0.000125)
     assert bench.bench_lr(0.0005, 1, 8) == 0.0005
+
+
+def test_bench_dump_outputs_fits_the_budget_and_samples_the_same_elements(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every tensor of the step's result as <name>.npy in float32 / float64, small arrays
+    whole, the larger ones as a fixed sample, all within the byte budget; two dumps of the same result are identical."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    out = {'cls_score': torch.randn(4, 300, 81, generator=g).bfloat16(), 'fc': torch.randn(4, 300, 1024, generator=g),
+           'num_detections': torch.tensor([100, 7, 0, 100], dtype=torch.int32), 'thresh': torch.rand(4, generator=g).double(),
+           'head': {'mask': torch.rand(5, generator=g) > 0.5}, 'note': 'not an array', 'class_dets': torch.zeros(2, 3)}
+    budget = 2 * 1000 * 1000
+    m1 = bench.dump_outputs(out, str(tmp_path / 'a'), budget=budget, skip=bench.DUMP_SKIP)
+    m2 = bench.dump_outputs(out, str(tmp_path / 'b'), budget=budget, skip=bench.DUMP_SKIP)
+    assert m1 == m2 and set(m1) == {'cls_score', 'fc', 'num_detections', 'thresh', 'head.mask'}
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == sorted(n + '.npy' for n in m1)
+    total = 0
+    for f in files:
+        x, y = np.load(str(tmp_path / 'a' / f)), np.load(str(tmp_path / 'b' / f))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= budget
+    assert m1['fc']['sampled'] and not m1['cls_score']['sampled']
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'a' / 'cls_score.npy')), out['cls_score'].float().numpy())
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'a' / 'num_detections.npy')), [100, 7, 0, 100])
+    fc = np.load(str(tmp_path / 'a' / 'fc.npy'))
+    assert fc.size == m1['fc']['elements_written'] and np.isin(fc, out['fc'].numpy().ravel()).all()
