@@ -155,6 +155,24 @@ int relnet_stem_bias_relu_pool(const void* in, const float* bias, void* out, int
 int relnet_stem_fused(const void* data, int in_dtype, const void* w256, const float* bias, void* out, int B, int H, int W,
                       void* stream);
 
+/* ---- the fused stem on the raw uint8 canvas (lib/utils/image.py:118-129 transform + tensor_vstack, then
+ * resnet_v1_101_rcnn_base.py:30-36): data [B,H,W,3] uint8 BGR HWC; inside im_info[b, :2] (device [B,3] fp32, null = whole
+ * canvas) RGB channel c is float(u8[.., 2-c] - mean[2-c]), outside 0.  Bit-identical to relnet_stem_fused on that fp32 tensor.  */
+int relnet_stem_fused_u8(const void* data, const float* im_info, double mean_b, double mean_g, double mean_r, const void* w256,
+                         const float* bias, void* out, int B, int H, int W, void* stream);
+
+/* ---- lib/utils/image.py:88-116 resize (cv2 INTER_LINEAR; dataset/image.py:resize restates it in float64, bit-identical here),
+ * batched over variable-size sources: src = B uint8 BGR HWC images back to back (src_bytes in all); table [B,6] int64 device
+ * (byte offset, h, w, flip, nh, nw), scale [B] float64 device (im_scale); out [B,Hc,Wc,3] uint8, the resized (optionally mirrored
+ * first, image.py:33) image at the top left of its slot, 0 elsewhere.  */
+int relnet_resize_u8(const void* src, long src_bytes, const long* table, const double* scale, void* out, int B, int Hc, int Wc,
+                     void* stream);
+
+/* ---- lib/utils/image.py:118-129 transform + tensor_vstack on the device: data [B,H,W,3] uint8 BGR HWC -> out [B,3,H,W]
+ * RGB NCHW (out_dtype 0 fp32 / 1 bf16), float(u8 - mean) inside im_info[b, :2] (null = whole canvas), 0 outside.  */
+int relnet_image_transform_u8(const void* data, const float* im_info, double mean_b, double mean_g, double mean_r, void* out,
+                              int out_dtype, int B, int H, int W, void* stream);
+
 /* ---- SYM_REL:46-83 extract_position_matrix + :29-44 extract_position_embedding + :109-116
  * pair_pos_fc1 + ReLU + the log(max(.,1e-6)) of :139, fused (the [N,M,64] embedding is never stored).
  * boxes [B,N,box_stride] with x1 at +box_off; wp_t [64, nmod*16] (embedding-index major), bp [nmod*16];

@@ -23,6 +23,7 @@ from . import ops
 UNITS = (3, 4, 23, 3)
 FILTERS = (256, 512, 1024, 2048)
 EPS = 1e-5
+PIXEL_MEANS = (103.06, 115.90, 123.15)      # network.PIXEL_MEANS (BGR) of every shipped experiment file
 
 
 def unit_names(fpn=False):
@@ -127,12 +128,14 @@ class Backbone(object):
     in torch.nn.functional.conv2d (used for the float32 parity path)."""
 
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', channels_last=True, impl=None, stem='hip', dcn=False,
-                 fpn=False, chain=True, frozen_only=False):
-        """frozen_only: pack conv1 + res2 only (what `forward_res2` runs): the part the training step never updates
+                 fpn=False, chain=True, frozen_only=False, pixel_means=PIXEL_MEANS):
+        """pixel_means: network.PIXEL_MEANS (BGR), subtracted on the device from uint8 [B,H,W,3] BGR HWC input (see `forward`).
+        frozen_only: pack conv1 + res2 only (what `forward_res2` runs): the part the training step never updates
         (cfgs/*.yaml FIXED_PARAMS) -- the Trainer keeps res3 .. heads in its own flat buffers, a second bf16 copy of them here would
         be a few hundred MB of stale weights."""
         self.dtype, self.device, self.dcn, self.fpn = dtype, device, dcn, fpn
         self.frozen_only = frozen_only
+        self.pixel_means = tuple(float(v) for v in pixel_means)
         self.use_chain = chain
         env = os.environ.get('RELNET_STAGE_SPLIT')        # A/B knob: '4:2,5:4' = stage:sub-batches ('0' / unset: no split)
         if env not in (None, '', '0'):
@@ -234,13 +237,21 @@ class Backbone(object):
         return ops.conv2d_nhwc(x, w, b, ksize=k, stride=stride, pad=pad, dil=dil, relu=relu, resid=resid,
                                out_dtype=out_dtype, w_frag=self.wf.get(name))
 
-    def forward_res2(self, data):
+    def _float_image(self, data, im_info, dtype):
+        """uint8 [B,H,W,3] BGR HWC -> [B,3,H,W] `dtype` RGB NCHW with the means subtracted inside each image's extent
+        (ops.image_transform_u8: what dataset/image.py:transform + tensor_vstack give); NCHW float input is returned as it is."""
+        if data.dtype != torch.uint8:
+            return data
+        return ops.image_transform_u8(data, self.pixel_means, im_info, dtype=dtype)
+
+    def forward_res2(self, data, im_info=None):
         """Stem + res2 only (the part the reference freezes in training: cfgs/*.yaml FIXED_PARAMS conv1 / res2): raw NCHW image ->
-        res2c output, NHWC bf16, on the inference kernels (fused stem, halo 3x3, chain kernels incl. res2a's in-kernel projection)."""
+        res2c output, NHWC bf16, on the inference kernels (fused stem, halo 3x3, chain kernels incl. res2a's in-kernel projection).
+        data and im_info as in `forward`."""
         if self.impl == 'hip32':           # float32 parity path (frozen_only backbones return the res2c map)
             assert self.frozen_only
-            return self._forward_hip32(data)
-        x = ops.stem_fused(data, self.w_stem, self.b32['conv1'])
+            return self._forward_hip32(self._float_image(data, im_info, torch.float32))
+        x = ops.stem_fused(data, self.w_stem, self.b32['conv1'], im_info, self.pixel_means)
         y_next = None
         self.last_chain_units = []
         for unit in self.units:
@@ -249,17 +260,17 @@ class Backbone(object):
             x, y_next = self._unit_hip(x, unit, y_next)
         return x
 
-    def _forward_hip(self, data, rpn_hook=None):
+    def _forward_hip(self, data, rpn_hook=None, im_info=None):
         if self.stem == 'hip':
-            # conv1 7x7/2 + bias + ReLU + pool1 in ONE kernel, raw NCHW image -> pooled NHWC map (no conv map in HBM)
-            x = ops.stem_fused(data, self.w_stem, self.b32['conv1'])
+            # conv1 7x7/2 + bias + ReLU + pool1 in ONE kernel, raw NCHW (or uint8 HWC) image -> pooled NHWC map (no conv map in HBM)
+            x = ops.stem_fused(data, self.w_stem, self.b32['conv1'], im_info, self.pixel_means)
         elif self.stem == 'hip3':
             # the three-launch form: repack to padded NHWC4, 7x7/2 conv + bias + ReLU on the MFMA kernel, then pool1
-            x = ops.stem_conv7(data, self.w_stem, self.b32['conv1'], relu=True)
+            x = ops.stem_conv7(self._float_image(data, im_info, torch.float32), self.w_stem, self.b32['conv1'], relu=True)
             x = ops.stem_bias_relu_pool(x, self.zero_bias64)
         else:
             # library 7x7 convolution (no bias), then ONE kernel for bias + ReLU + pool1
-            x = data.to(self.dtype).contiguous(memory_format=self.mf)
+            x = self._float_image(data, im_info, torch.float32).to(self.dtype).contiguous(memory_format=self.mf)
             x = F.conv2d(x, self.w['conv1'][0], None, stride=2, padding=3)
             x = ops.stem_bias_relu_pool(x.permute(0, 2, 3, 1), self.b32['conv1'])
         conv4 = None
@@ -444,8 +455,12 @@ class Backbone(object):
         return dict(conv4=nchw(conv4), conv5=nchw(conv5), conv_new_1_relu=nchw(feat),
                     rpn_cls_score=nchw(rpn[..., :na2]), rpn_bbox_pred=nchw(rpn[..., na2:]))
 
-    def forward(self, data, rpn_hook=None):
-        """data [B,3,H,W] -> dict(conv4, conv5, conv_new_1_relu, rpn_cls_score, rpn_bbox_pred)
+    def forward(self, data, rpn_hook=None, im_info=None):
+        """data [B,3,H,W] float NCHW (RGB, means subtracted: dataset/image.py:get_image), or [B,H,W,3] uint8 BGR HWC as decoded /
+        resized (ops.resize_u8): the means (`pixel_means`) are then subtracted on the device inside each image's extent im_info[:, :2]
+        ([B,3] fp32 device; None = the whole canvas) and the rest reads 0, which is the reference's padding rule -- the fused stem
+        reads the uint8 canvas itself (relnet_stem_fused_u8), every other path converts it first (relnet_image_transform_u8).
+        -> dict(conv4, conv5, conv_new_1_relu, rpn_cls_score, rpn_bbox_pred)
         (logical NCHW tensors; channels-last memory).
 
         rpn_hook (impl 'hip'): callable(rpn_cls_score, rpn_bbox_pred) -> anything, e.g. the proposal operator.  The RPN head
@@ -453,10 +468,10 @@ class Backbone(object):
         stream (the proposal kernels are latency bound and occupy ~54 workgroups; res5 fills the rest of the GPU); the two
         streams join before this function returns and the hook's result is returned under the key 'rpn_hook'."""
         if self.impl == 'hip':
-            return self._forward_hip(data, rpn_hook)
+            return self._forward_hip(data, rpn_hook, im_info)
         if self.impl == 'hip32':
-            return self._forward_hip32(data)
-        x = data.to(self.dtype).contiguous(memory_format=self.mf)
+            return self._forward_hip32(self._float_image(data, im_info, torch.float32))
+        x = self._float_image(data, im_info, torch.float32).to(self.dtype).contiguous(memory_format=self.mf)
         x = self._conv(x, 'conv1', stride=2, pad=3, relu=True)
         x = F.max_pool2d(x, kernel_size=3, stride=2, padding=0, ceil_mode=True)
         conv4 = None

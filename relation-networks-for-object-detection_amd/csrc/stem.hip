@@ -298,3 +298,187 @@ extern "C" int relnet_stem_fused(const void* data, int in_dtype, const void* w25
   stem_fused_kernel<<<(unsigned)((long)B * g.tiles_y * g.tiles_x), 512, lds, (hipStream_t)stream>>>(g);
   return check_launch("relnet_stem_fused");
 }
+
+// ---------------------------------------------------------------------------------------
+// Fused stem on the raw uint8 canvas: the same kernel as stem_fused_kernel (tile, LDS layout, MFMA body, epilogue and pool are
+// the same code) with another prologue -- the window is read from [B, H, W, 3] uint8 BGR HWC and every pixel is made into the
+// value the fp32 path reads from the tensor of dataset/image.py:transform + tensor_vstack (lib/utils/image.py:118-129):
+//   RGB channel c of pixel (y, x) = float(u8[y, x, 2 - c] - mean[2 - c]) inside the image's extent im_info[b, :2] (the stride
+//   padding, u8 = 0 there, becomes -mean like in the reference), 0 outside it (tensor_vstack's batch padding) -- then bf16 through
+//   the same pack_bf16x2.  (double)u8 - mean is exact, so the one rounding to float is numpy's float32(u8 - mean_f64): the pooled
+//   map is bit-identical to relnet_stem_fused on that fp32 tensor, for a quarter of the bytes read.
+// The fp32 kernel is left as it is rather than templated on its loader, so that its code generation cannot move.
+// ---------------------------------------------------------------------------------------
+namespace relnet {
+
+struct StemFusedU8Args {
+  const unsigned char* in;            // [B, H, W, 3] uint8 BGR HWC
+  const float* im_info;               // [B, 3] (rows, cols, scale) or null = the whole canvas
+  const unsigned short* w256;         // [64][256] bf16, k = ty * 32 + tx * 4 + c (ops.pack_stem_weight)
+  const float* bias;                  // [64]
+  unsigned short* out;                // [B, Hp, Wp, 64] bf16
+  double mean[3];                     // BGR
+  int B, H, W, Hc, Wc, Hp, Wp, tiles_y, tiles_x;
+};
+
+__global__ __launch_bounds__(512) void stem_fused_u8_kernel(StemFusedU8Args g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned short* sIn = (unsigned short*)smem;                                   // [39][64][4]
+  unsigned short* sW = (unsigned short*)(smem + kSfIY * kSfIX * 8);              // [14][2][64 lanes][8]
+  unsigned short* sOut = (unsigned short*)smem;                                  // [512][kSfOutLd] (after the MFMAs)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, half = lane >> 5;
+  int t = blockIdx.x;
+  const int tx = t % g.tiles_x; t /= g.tiles_x;
+  const int ty = t % g.tiles_y;
+  const int b = t / g.tiles_y;
+  const int cy0 = ty * 2 * kSfPY, cx0 = tx * 2 * kSfPX;
+  const int iy0 = 2 * cy0 - 3, ix0 = 2 * cx0 - 3;
+
+  // ---- prologue: every global load (4 weight chunks, the image extent, 15 bytes of pixels per thread) is issued before the first
+  // one is consumed, as in stem_fused_kernel (r06).  Out-of-range pixels load a clamped address and are zeroed afterwards.
+  constexpr int kWIt = (kSfKS * 2 * 64 + 511) / 512;
+  constexpr int kPIt = (kSfIY * kSfIX + 511) / 512;
+  uint4 wv[kWIt];
+#pragma unroll
+  for (int it = 0; it < kWIt; ++it) {
+    const int c = min(tid + 512 * it, kSfKS * 2 * 64 - 1);
+    const int l = c & 63, nt = (c >> 6) & 1, kk = c >> 7;
+    const int k = (kk >> 1) * 32 + (kk & 1) * 16 + 8 * (l >> 5);
+    wv[it] = *(const uint4*)(g.w256 + (32 * nt + (l & 31)) * 256 + k);
+  }
+  float ext_h = (float)g.H, ext_w = (float)g.W;
+  if (g.im_info) { ext_h = g.im_info[3 * b]; ext_w = g.im_info[3 * b + 1]; }
+  unsigned char pv[kPIt][3];
+  int pyx[kPIt][2];
+  bool pok[kPIt];
+#pragma unroll
+  for (int it = 0; it < kPIt; ++it) {
+    const int p = tid + 512 * it;
+    const int wy = p / kSfIX, wx = p - wy * kSfIX;
+    const int y = iy0 + wy, x = ix0 + wx;
+    pok[it] = p < kSfIY * kSfIX && wx < kSfIX - 1 && y >= 0 && y < g.H && x >= 0 && x < g.W;
+    pyx[it][0] = y; pyx[it][1] = x;
+    const unsigned char* q = g.in + (((long)b * g.H + min(max(y, 0), g.H - 1)) * g.W + min(max(x, 0), g.W - 1)) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pv[it][c] = q[c];
+  }
+  const int eh = min(g.H, (int)ext_h), ew = min(g.W, (int)ext_w);
+#pragma unroll
+  for (int it = 0; it < kWIt; ++it) {
+    const int c = tid + 512 * it;
+    if (c < kSfKS * 2 * 64) *(uint4*)(sW + (long)c * 8) = wv[it];
+  }
+#pragma unroll
+  for (int it = 0; it < kPIt; ++it) {
+    const int p = tid + 512 * it;
+    const bool in = pyx[it][0] < eh && pyx[it][1] < ew;
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = in ? (float)((double)pv[it][2 - c] - g.mean[2 - c]) : 0.f;
+    if (p < kSfIY * kSfIX)
+      *(uint2*)(sIn + (long)p * 4) = pok[it] ? make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], 0.f)) : make_uint2(0u, 0u);
+  }
+  __syncthreads();
+
+  // ---- MFMAs, bias + ReLU, pool1: as in stem_fused_kernel
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  int pbase[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    int m = wave * 64 + j * 32 + l31;
+    m = m < kSfCY * kSfCX ? m : 0;
+    const int cy = m / kSfCX, cx = m - cy * kSfCX;
+    pbase[j] = ((2 * cy) * kSfIX + 2 * cx + 2 * half) * 4;
+  }
+#pragma unroll
+  for (int kk = 0; kk < kSfKS; ++kk) {
+    const int tyy = kk >> 1, txo = (kk & 1) * 4;
+    bf16x8 wf[2], pf[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) wf[i] = *(const bf16x8*)(sW + ((kk * 2 + i) * 64 + lane) * 8);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) pf[j] = *(const bf16x8*)(sIn + pbase[j] + (tyy * kSfIX + txo) * 4);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], pf[j], acc[i][j], 0, 0, 0);
+  }
+  __syncthreads();
+
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = wave * 64 + j * 32 + l31;
+    const int cy = m / kSfCX, cx = m - cy * kSfCX;
+    const bool live = m < kSfCY * kSfCX && cy0 + cy < g.Hc && cx0 + cx < g.Wc;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const int ch = 32 * i + 8 * gq + 4 * half;
+        const float4 bv = *(const float4*)(g.bias + ch);
+        float v0 = fmaxf(acc[i][j][4 * gq] + bv.x, 0.f), v1 = fmaxf(acc[i][j][4 * gq + 1] + bv.y, 0.f);
+        float v2 = fmaxf(acc[i][j][4 * gq + 2] + bv.z, 0.f), v3 = fmaxf(acc[i][j][4 * gq + 3] + bv.w, 0.f);
+        if (!live) { v0 = v1 = v2 = v3 = 0.f; }
+        *(uint2*)(sOut + (long)m * kSfOutLd + ch) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+      }
+  }
+  __syncthreads();
+
+  for (int it = tid; it < kSfPY * kSfPX * 8; it += 512) {
+    const int cg = it & 7, pp = it >> 3;
+    const int py = pp / kSfPX, px = pp - py * kSfPX;
+    const int oy = ty * kSfPY + py, ox = tx * kSfPX + px;
+    if (oy >= g.Hp || ox >= g.Wp) continue;
+    float best[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) best[e] = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const uint4 v = *(const uint4*)(sOut + (long)((2 * py + dy) * kSfCX + 2 * px + dx) * kSfOutLd + cg * 8);
+        const unsigned int w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          best[2 * e] = fmaxf(best[2 * e], bf2f(w4[e] & 0xffff));
+          best[2 * e + 1] = fmaxf(best[2 * e + 1], bf2f(w4[e] >> 16));
+        }
+      }
+    *(uint4*)(g.out + (((long)b * g.Hp + oy) * g.Wp + ox) * 64 + cg * 8) =
+        make_uint4(pack_bf16x2(best[0], best[1]), pack_bf16x2(best[2], best[3]), pack_bf16x2(best[4], best[5]), pack_bf16x2(best[6], best[7]));
+  }
+}
+
+}  // namespace relnet
+
+// data [B,H,W,3] uint8 BGR HWC, im_info [B,3] fp32 device (null: every image fills the canvas), means in BGR order; the rest as
+// relnet_stem_fused.
+extern "C" int relnet_stem_fused_u8(const void* data, const float* im_info, double mean_b, double mean_g, double mean_r,
+                                    const void* w256, const float* bias, void* out, int B, int H, int W, void* stream) {
+  RELNET_REQUIRE(data && w256 && bias && out, "relnet_stem_fused_u8: null operand");
+  RELNET_REQUIRE(B > 0 && H >= 7 && W >= 7, "relnet_stem_fused_u8: bad shape");
+  RELNET_REQUIRE(((uintptr_t)w256 & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)bias & 15) == 0, "relnet_stem_fused_u8: operands must be 16-byte aligned");
+  StemFusedU8Args g;
+  g.in = (const unsigned char*)data; g.im_info = im_info; g.w256 = (const unsigned short*)w256; g.bias = bias;
+  g.out = (unsigned short*)out;
+  g.mean[0] = mean_b; g.mean[1] = mean_g; g.mean[2] = mean_r;
+  g.B = B; g.H = H; g.W = W;
+  g.Hc = (H + 6 - 7) / 2 + 1; g.Wc = (W + 6 - 7) / 2 + 1;
+  g.Hp = (g.Hc - 3 + 1) / 2 + 1; g.Wp = (g.Wc - 3 + 1) / 2 + 1;
+  if ((g.Hp - 1) * 2 >= g.Hc) --g.Hp;
+  if ((g.Wp - 1) * 2 >= g.Wc) --g.Wp;
+  g.tiles_y = (g.Hp + kSfPY - 1) / kSfPY; g.tiles_x = (g.Wp + kSfPX - 1) / kSfPX;
+  const size_t lds = (size_t)512 * kSfOutLd * 2;
+  static relnet::PerDeviceOnce attr_once;
+  if (attr_once.first()) hipFuncSetAttribute((const void*)stem_fused_u8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  stem_fused_u8_kernel<<<(unsigned)((long)B * g.tiles_y * g.tiles_x), 512, lds, (hipStream_t)stream>>>(g);
+  return check_launch("relnet_stem_fused_u8");
+}

@@ -4,3 +4,4 @@ Host-side Python like the reference's `lib/dataset`, `lib/utils/image.py`, `core
 tensors are handed to the HIP path as torch device tensors."""
 from .imdb import IMDB  # noqa: F401
 from .coco import coco  # noqa: F401
+from .image import device_images, resize_plan  # noqa: F401

@@ -35,14 +35,25 @@ def _bilinear_axis(n_src, n_dst, scale):
     return i0, np.minimum(i0 + 1, n_src - 1), w1
 
 
-def resize(im, target_size, max_size, stride=0):
-    """image.py:78-108.  Returns (resized [+ padded] float image, im_scale)."""
-    h, w = im.shape[:2]
+def resize_plan(h, w, target_size, max_size, stride=0):
+    """The host arithmetic of `resize` (image.py:78-108) for an h x w source: (im_scale, nh, nw, ph, pw) -- the scale, the resized
+    size and the size after zero-padding to a multiple of `stride` (= nh, nw for stride 0)."""
     size_min, size_max = min(h, w), max(h, w)
     im_scale = float(target_size) / float(size_min)
     if np.round(im_scale * size_max) > max_size:
         im_scale = float(max_size) / float(size_max)
     nw, nh = int(round(w * im_scale)), int(round(h * im_scale))
+    if stride == 0:
+        return im_scale, nh, nw, nh, nw
+    ph = int(np.ceil(nh / float(stride)) * stride)
+    pw = int(np.ceil(nw / float(stride)) * stride)
+    return im_scale, nh, nw, ph, pw
+
+
+def resize(im, target_size, max_size, stride=0):
+    """image.py:78-108.  Returns (resized [+ padded] float image, im_scale)."""
+    h, w = im.shape[:2]
+    im_scale, nh, nw, ph, pw = resize_plan(h, w, target_size, max_size, stride)
     x0, x1, wx = _bilinear_axis(w, nw, im_scale)
     y0, y1, wy = _bilinear_axis(h, nh, im_scale)
     src = im.astype(np.float64)
@@ -54,8 +65,6 @@ def resize(im, target_size, max_size, stride=0):
     out = out.astype(np.float32)
     if stride == 0:
         return out, im_scale
-    ph = int(np.ceil(out.shape[0] / float(stride)) * stride)
-    pw = int(np.ceil(out.shape[1] / float(stride)) * stride)
     padded = np.zeros((ph, pw, out.shape[2]), dtype=out.dtype)
     padded[:out.shape[0], :out.shape[1], :] = out
     return padded, im_scale
@@ -77,24 +86,55 @@ def clip_boxes(boxes, im_shape):
     return boxes
 
 
-def get_image(roidb, config, rng=random):
-    """image.py:16-45: -> (list of [1,3,H,W] float32 arrays, roidb copies with scaled `boxes` and `im_info`)."""
+def get_image(roidb, config, rng=random, raw=False):
+    """image.py:16-45: -> (list of [1,3,H,W] float32 arrays, roidb copies with scaled `boxes` and `im_info`).
+    raw=True: no pixel work -- the list holds (decoded uint8 BGR HWC source, flipped, im_scale, nh, nw) per image instead (the resize,
+    mirror and transform are left to the device: pack_raw + device_images); `im_info` and the boxes are the same as without it."""
     ims, out = [], []
     for rec in roidb:
         assert os.path.exists(rec['image']), '%s does not exist' % rec['image']
         im = imread_bgr(rec['image'])
-        if rec['flipped']:
-            im = im[:, ::-1, :]
         new = dict(rec)
         target_size, max_size = config.SCALES[rng.randrange(len(config.SCALES))]
-        im, im_scale = resize(im, target_size, max_size, stride=config.network.IMAGE_STRIDE)
-        t = transform(im, config.network.PIXEL_MEANS)
-        ims.append(t)
-        im_info = [t.shape[2], t.shape[3], im_scale]
+        if raw:
+            assert im.dtype == np.uint8, 'raw images: uint8 sources only (%s is %s)' % (rec['image'], im.dtype)
+            im_scale, nh, nw, ph, pw = resize_plan(im.shape[0], im.shape[1], target_size, max_size, config.network.IMAGE_STRIDE)
+            ims.append((im, bool(rec['flipped']), im_scale, nh, nw))
+            im_info = [ph, pw, im_scale]
+        else:
+            if rec['flipped']:
+                im = im[:, ::-1, :]
+            im, im_scale = resize(im, target_size, max_size, stride=config.network.IMAGE_STRIDE)
+            t = transform(im, config.network.PIXEL_MEANS)
+            ims.append(t)
+            im_info = [t.shape[2], t.shape[3], im_scale]
         new['boxes'] = clip_boxes(np.round(rec['boxes'].astype(np.float64).copy() * im_scale), im_info[:2])
         new['im_info'] = im_info
         out.append(new)
     return ims, out
+
+
+def pack_raw(raws, im_info):
+    """The raw-image part of a batch (get_image(raw=True)): a dict of `image_src` (the uint8 sources back to back, flat),
+    `image_table` [B,6] int64 (byte offset, h, w, flip, nh, nw), `image_scale` [B] float64 and `canvas_hw`, a host tuple (Hc, Wc):
+    the batch maximum of the padded extents im_info[:, :2], which is what tensor_vstack gives the float batch."""
+    table = np.zeros((len(raws), 6), dtype=np.int64)
+    off = 0
+    for i, (im, flip, im_scale, nh, nw) in enumerate(raws):
+        table[i] = (off, im.shape[0], im.shape[1], int(flip), nh, nw)
+        off += im.size
+    src = np.concatenate([np.ascontiguousarray(r[0]).reshape(-1) for r in raws])
+    info = np.asarray(im_info)
+    canvas = (int(info[:, 0].max()), int(info[:, 1].max()))
+    return dict(image_src=src, image_table=table, image_scale=np.array([r[2] for r in raws], dtype=np.float64), canvas_hw=canvas)
+
+
+def device_images(batch):
+    """The uint8 canvas [B,Hc,Wc,3] BGR HWC of a raw-image batch (a loader's batch with raw_images=True, on the GPU): the sources
+    resized (and mirrored) by ops.resize_u8 into the top left of their slots, zeros elsewhere.  The detector and the trainers take it
+    as `data` with the batch's `im_info`, which gives every image its extent.  No host synchronisation."""
+    from .. import ops
+    return ops.resize_u8(batch['image_src'], batch['image_table'], batch['image_scale'], batch['canvas_hw'])
 
 
 def tensor_vstack(tensor_list, pad=0):

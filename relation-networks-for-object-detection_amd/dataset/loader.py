@@ -12,11 +12,16 @@
 Shuffling with aspect-ratio grouping is the reference's (:496-513): horizontal and vertical images are permuted
 separately, batches are formed inside a group, then the batches are permuted.
 Batches are dicts of torch tensors (host); `.cuda()` them or pass `device=`.
+
+raw_images=True (every loader): no pixel work on the host.  The loader decodes each image and plans its resize
+(image.resize_plan); instead of `data` the batch carries the uint8 sources and their resize table (image.pack_raw: image_src,
+image_table, image_scale, canvas_hw), and `dataset.device_images(batch)` makes the uint8 canvas on the GPU that the detector and
+the trainers take as `data`.  im_info, gt_boxes and proposals are the same as without it.
 """
 import numpy as np
 import torch
 
-from .image import get_image, tensor_vstack
+from .image import get_image, pack_raw, tensor_vstack
 
 
 def _gt_boxes(rec):
@@ -41,7 +46,8 @@ def _pad_rows(arrs, width, fill=0.0):
 class _Iter(object):
     drop_last = True
 
-    def __init__(self, roidb, config, batch_size, shuffle, aspect_grouping, seed, device):
+    def __init__(self, roidb, config, batch_size, shuffle, aspect_grouping, seed, device, raw_images=False):
+        self.raw_images = raw_images
         self.roidb, self.cfg, self.batch_size = roidb, config, batch_size
         self.shuffle, self.aspect_grouping, self.device = shuffle, aspect_grouping, device
         self.size = len(roidb)
@@ -74,6 +80,15 @@ class _Iter(object):
     def __len__(self):
         return self.size // self.batch_size if self.drop_last else -(-self.size // self.batch_size)
 
+    def _images(self, recs):
+        """get_image for this loader -> (roidb copies, dict of the image part of the batch, (H, W) of the batch)."""
+        ims, recs = get_image(recs, self.cfg, raw=self.raw_images)
+        if self.raw_images:
+            d = pack_raw(ims, [r['im_info'] for r in recs])
+            return recs, d, d['canvas_hw']
+        data = tensor_vstack(ims)
+        return recs, dict(data=data), data.shape[2:]
+
     def _tensors(self, d):
         return {k: (torch.as_tensor(v).to(self.device) if isinstance(v, np.ndarray) else v) for k, v in d.items()}
 
@@ -82,9 +97,9 @@ class TestLoader(_Iter):
     drop_last = False
     __test__ = False          # not a pytest class
 
-    def __init__(self, roidb, config, batch_size=1, shuffle=False, has_rpn=False, device='cpu'):
+    def __init__(self, roidb, config, batch_size=1, shuffle=False, has_rpn=False, device='cpu', raw_images=False):
         self.has_rpn = has_rpn
-        super(TestLoader, self).__init__(roidb, config, batch_size, shuffle, False, 0, device)
+        super(TestLoader, self).__init__(roidb, config, batch_size, shuffle, False, 0, device, raw_images)
 
     def __next__(self):
         if self.cur >= self.size:
@@ -92,9 +107,8 @@ class TestLoader(_Iter):
         lo, hi = self.cur, min(self.cur + self.batch_size, self.size)
         recs = [self.roidb[self.index[i]] for i in range(lo, hi)]
         self.cur += self.batch_size
-        ims, recs = get_image(recs, self.cfg)
-        out = dict(data=tensor_vstack(ims), im_info=np.array([r['im_info'] for r in recs], dtype=np.float32),
-                   index=[int(self.index[i]) for i in range(lo, hi)])
+        recs, out, _ = self._images(recs)
+        out.update(im_info=np.array([r['im_info'] for r in recs], dtype=np.float32), index=[int(self.index[i]) for i in range(lo, hi)])
         if not self.has_rpn:          # get_rcnn_testbatch: the image's own proposals (already scaled by get_image)
             out['proposals'], out['num_proposals'] = _pad_rows([r['boxes'].astype(np.float32) for r in recs], 4)
         return self._tensors(out)
@@ -110,12 +124,12 @@ def _conv4_size(n):
 
 class AnchorLoader(_Iter):
     def __init__(self, roidb, config, batch_size=1, shuffle=False, aspect_grouping=False, seed=0, device='cpu',
-                 feat_shape_fn=None, device_targets=False):
+                 feat_shape_fn=None, device_targets=False, raw_images=False):
         """device_targets: leave `assign_anchor` to the trainer (relnet_assign_anchor on the GPU, Trainer.rpn_targets): the
         batch then carries only data / im_info / gt_boxes / num_gt and the loader does no per-anchor work on the host."""
         self.device_targets = device_targets
         self.feat_shape_fn = feat_shape_fn or (lambda h, w: (_conv4_size(h), _conv4_size(w)))
-        super(AnchorLoader, self).__init__(roidb, config, batch_size, shuffle, aspect_grouping, seed, device)
+        super(AnchorLoader, self).__init__(roidb, config, batch_size, shuffle, aspect_grouping, seed, device, raw_images)
 
     def __next__(self):
         from .. import train
@@ -123,9 +137,7 @@ class AnchorLoader(_Iter):
             raise StopIteration
         recs = [self.roidb[self.index[i]] for i in range(self.cur, self.cur + self.batch_size)]
         self.cur += self.batch_size
-        ims, recs = get_image(recs, self.cfg)
-        data = tensor_vstack(ims)
-        H, W = data.shape[2], data.shape[3]
+        recs, images, (H, W) = self._images(recs)
         tc = train.TrainConfig()
         tc.anchor_scales, tc.anchor_ratios = tuple(self.cfg.network.ANCHOR_SCALES), tuple(self.cfg.network.ANCHOR_RATIOS)
         tc.rpn_batch_size, tc.rpn_fg_fraction = self.cfg.TRAIN.RPN_BATCH_SIZE, self.cfg.TRAIN.RPN_FG_FRACTION
@@ -133,7 +145,7 @@ class AnchorLoader(_Iter):
         gts = [_gt_boxes(r) for r in recs]
         if self.device_targets:
             gt_pad, num_gt = _pad_rows(gts, 5)
-            return self._tensors(dict(data=data, im_info=np.array([r['im_info'] for r in recs], dtype=np.float32),
+            return self._tensors(dict(images, im_info=np.array([r['im_info'] for r in recs], dtype=np.float32),
                                       gt_boxes=gt_pad, num_gt=num_gt))
         fh, fw = self.feat_shape_fn(H, W)
         labs, tgts, wgts = [], [], []
@@ -141,20 +153,20 @@ class AnchorLoader(_Iter):
             L, T, Wt = train.assign_anchor((fh, fw), gt, (r['im_info'][0], r['im_info'][1]), tc, seed=int(self.rng.randint(1 << 30)))
             labs.append(L); tgts.append(T); wgts.append(Wt)
         gt_pad, num_gt = _pad_rows(gts, 5)
-        return self._tensors(dict(data=data, im_info=np.array([r['im_info'] for r in recs], dtype=np.float32), gt_boxes=gt_pad,
+        return self._tensors(dict(images, im_info=np.array([r['im_info'] for r in recs], dtype=np.float32), gt_boxes=gt_pad,
                                   num_gt=num_gt, label=np.stack(labs), bbox_target=np.stack(tgts), bbox_weight=np.stack(wgts)))
 
 
 class ROIIter(_Iter):
-    def __init__(self, roidb, config, batch_size=1, shuffle=False, aspect_grouping=False, seed=0, device='cpu'):
-        super(ROIIter, self).__init__(roidb, config, batch_size, shuffle, aspect_grouping, seed, device)
+    def __init__(self, roidb, config, batch_size=1, shuffle=False, aspect_grouping=False, seed=0, device='cpu', raw_images=False):
+        super(ROIIter, self).__init__(roidb, config, batch_size, shuffle, aspect_grouping, seed, device, raw_images)
 
     def __next__(self):
         if self.cur + self.batch_size > self.size:
             raise StopIteration
         recs = [self.roidb[self.index[i]] for i in range(self.cur, self.cur + self.batch_size)]
         self.cur += self.batch_size
-        ims, recs = get_image(recs, self.cfg)
+        recs, images, _ = self._images(recs)
         props, gts = [], []
         for r in recs:
             is_gt = np.asarray(r.get('is_gt', np.zeros(len(r['boxes'])))) > 0
@@ -171,5 +183,5 @@ class ROIIter(_Iter):
         if top > 0:
             p_pad, num_p = p_pad[:-1], num_p[:-1]
         gt_pad, num_gt = _pad_rows(gts, 5)
-        return self._tensors(dict(data=tensor_vstack(ims), im_info=np.array([r['im_info'] for r in recs], dtype=np.float32),
+        return self._tensors(dict(images, im_info=np.array([r['im_info'] for r in recs], dtype=np.float32),
                                   proposals=p_pad, num_proposals=num_p, gt_boxes=gt_pad, num_gt=num_gt))

@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import ops
-from .backbone import Backbone
+from .backbone import Backbone, PIXEL_MEANS
 from .relation import RelationHead
 from .learn_nms import LearnNMS
 from .operator_py.proposal import generate_anchors, propose_batch
@@ -41,6 +41,7 @@ class Config(object):
     dcn_trans_std = 0.1
     roi_align = False         # True: ROIAlign (ops.roi_align, sampling_ratio 2) feeds fc_new_1 instead of the graphs' ROIPooling -- the operator
     roi_align_sampling = 2    # north_star names; no reference graph uses it (SYM_REL:252-253 is ROIPooling), so it is off by default
+    pixel_means = PIXEL_MEANS  # network.PIXEL_MEANS (BGR): subtracted on the device when the detector is given uint8 images
 
     @classmethod
     def from_experiment(cls, name, train=False):
@@ -55,6 +56,7 @@ class Config(object):
         c.experiment = name
         c.symbol = e.symbol
         c.feat_stride = n.RPN_FEAT_STRIDE
+        c.pixel_means = tuple(float(v) for v in n.PIXEL_MEANS)
         c.anchor_scales, c.anchor_ratios = tuple(n.ANCHOR_SCALES), tuple(n.ANCHOR_RATIOS)
         c.num_classes = e.dataset.NUM_CLASSES
         c.nms_target_thresh = tuple(float(v) for v in str(n.NMS_TARGET_THRESH).split(','))
@@ -103,7 +105,7 @@ class Detector(object):
         # (3.3 -> 4.5 ms, r02), so eager calls fork from 3 images.  None = that rule; RELNET_OVERLAP_MIN_IMAGES overrides it.
         env = os.environ.get('RELNET_OVERLAP_MIN_IMAGES')
         self.overlap_min_images = int(env) if env else None
-        self.backbone = Backbone(params, dtype, device, stem=stem, dcn=self.cfg.dcn)
+        self.backbone = Backbone(params, dtype, device, stem=stem, dcn=self.cfg.dcn, pixel_means=self.cfg.pixel_means)
         if self.cfg.dcn:          # FC 12544 -> 2*7*7 offsets (SYM_DCN_RELNMS:1075), columns in (ph, pw, c) order
             self.w_offset = params['offset_weight'][:, fc1_channels_last_perm()].to(device, dtype).contiguous()
             self.b_offset = params['offset_bias'].to(device, torch.float32).contiguous()
@@ -127,7 +129,8 @@ class Detector(object):
         return cls(ck.merge_params(arg, aux), **kw)
 
     def forward(self, data, im_info, post=True, keep_features=False):
-        """data [B,3,H,W], im_info [B,3] fp32 (device).  No host synchronisation inside.
+        """data [B,3,H,W] float NCHW, or [B,H,W,3] uint8 BGR HWC (the canvas of dataset.device_images / ops.resize_u8: the means
+        cfg.pixel_means are subtracted on the device, Backbone.forward), im_info [B,3] fp32 (device).  No host synchronisation inside.
         keep_features: also return the backbone maps of THIS call under 'features' (conv4, conv5, conv_new_1_relu, RPN maps)
         and the head's intermediates (attention_1/2, fc_all_1/2_relu) under 'head' -- what oracle/parity.py checks."""
         c = self.cfg
@@ -141,10 +144,10 @@ class Detector(object):
         if self.overlap_rpn and self.backbone.impl == 'hip' and B >= min_images:   # RPN head + proposal on a side stream, beside res5
             # (under hipGraph replay the fork / join are graph edges: at one image per step 3.0 -> 2.75-2.80 ms, at two 3.63 -> 3.30 ms,
             #  r03 A/B with RELNET_OVERLAP_MIN_IMAGES; round 2's eager-mode measurement had said the opposite)
-            f = self.backbone.forward(data, rpn_hook=propose)
+            f = self.backbone.forward(data, rpn_hook=propose, im_info=im_info)
             rois, roi_scores, num_kept = f['rpn_hook']
         else:
-            f = self.backbone.forward(data)
+            f = self.backbone.forward(data, im_info=im_info)
             rois, roi_scores, num_kept = propose(f['rpn_cls_score'], f['rpn_bbox_pred'])
         N = rois.shape[1]
         if c.dcn:                 # SYM_DCN_RELNMS:1073-1080
@@ -261,7 +264,7 @@ class FPNDetector(object):
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', cfg=None, relation=True, stem='hip'):
         self.cfg = cfg or Config()
         self.dtype, self.device = dtype, device
-        self.backbone = Backbone(params, dtype, device, stem=stem, fpn=True)
+        self.backbone = Backbone(params, dtype, device, stem=stem, fpn=True, pixel_means=self.cfg.pixel_means)
         self.head = RelationHead(params, dtype, device, fc1_perm=fc1_channels_last_perm(), use_relation=relation,
                                  fc_names=('roi_pool_fc1', 'roi_pool_fc2'))
         self.lnms = None
@@ -273,13 +276,13 @@ class FPNDetector(object):
     pad_empty_levels = True
 
     def forward(self, data, proposals, im_info, post=True, num_proposals=None):
-        """data [B,3,H,W] (H, W multiples of 32); proposals [B,N,4] fp32 xyxy; im_info [B,3]; num_proposals [B] int32
+        """data [B,3,H,W] float NCHW or [B,H,W,3] uint8 BGR HWC (as Detector.forward; H, W multiples of 32); proposals [B,N,4] fp32 xyxy; im_info [B,3]; num_proposals [B] int32
         (optional, device): valid rows of `proposals` per image.  No host synchronisation inside."""
         c = self.cfg
         B, N = proposals.shape[:2]
-        if data.shape[2] % 32 or data.shape[3] % 32:
+        if any(n % 32 for n in ops.image_hw(data)):
             raise ValueError("FPN images must be padded to IMAGE_STRIDE 32, got %s" % (tuple(data.shape),))
-        f = self.backbone.forward(data)
+        f = self.backbone.forward(data, im_info=im_info)
         n_rows = None
         if self.pad_empty_levels or num_proposals is not None:
             rois, level, perm, counts, n_rows = ops.fpn_roi_dispatch(proposals.contiguous(), n_valid=num_proposals,

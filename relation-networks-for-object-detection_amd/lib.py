@@ -20,7 +20,7 @@ class RelnetError(RuntimeError):
 
 _lib = None
 
-_vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
+_vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
 _SIGNATURES = {
     'relnet_version': (C.c_int, []),
@@ -140,6 +140,9 @@ _SIGNATURES = {
     'relnet_lnms_score': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     'relnet_stem_fused': (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'relnet_stem_fused_u8': (C.c_int, [_vp, _vp, _d, _d, _d, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'relnet_resize_u8': (C.c_int, [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'relnet_image_transform_u8': (C.c_int, [_vp, _vp, _d, _d, _d, _vp, _i, _i, _i, _i, _vp]),
     'relnet_stem_pack_input': (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'relnet_stem_conv7': (C.c_int, [_vp, _vp, _vp, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'relnet_proposal_target': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),

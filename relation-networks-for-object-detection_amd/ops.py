@@ -674,21 +674,89 @@ def stem_bias_relu_pool(x_nhwc, bias, ksize=3, stride=2):
     return out
 
 
-def stem_fused(data, w256, bias):
-    """data [B,3,H,W] fp32/bf16 NCHW -> relu(pool1(relu(conv1 7x7/2 + bias))) as NHWC bf16 [B,Hp,Wp,64] in ONE kernel
-    (csrc/stem.hip:stem_fused_kernel): bit-identical to stem_conv7(relu=True) + stem_bias_relu_pool(zero bias)."""
-    _chk(data, w256, bias)
-    data = data.contiguous()
-    B, Cin, H, W = data.shape
-    assert Cin == 3 and w256.shape == (64, 256) and w256.dtype == torch.bfloat16 and bias.dtype == torch.float32
+def _stem_pooled_hw(H, W):
     Hc, Wc = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     Hp, Wp = -(-(Hc - 3) // 2) + 1, -(-(Wc - 3) // 2) + 1
     if (Hp - 1) * 2 >= Hc:
         Hp -= 1
     if (Wp - 1) * 2 >= Wc:
         Wp -= 1
+    return Hp, Wp
+
+
+def image_hw(data):
+    """(H, W) of an image batch in either layout the detector takes: [B,3,H,W] float NCHW or [B,H,W,3] uint8 BGR HWC."""
+    return (data.shape[1], data.shape[2]) if data.dtype == torch.uint8 else (data.shape[2], data.shape[3])
+
+
+def _means(pixel_means):
+    m = [float(v) for v in pixel_means]
+    assert len(m) == 3, "pixel_means: three values in BGR order"
+    return m
+
+
+def _im_info_ptr(im_info, B):
+    if im_info is None:
+        return 0
+    _chk(im_info)
+    assert im_info.dtype == torch.float32 and im_info.is_contiguous() and tuple(im_info.shape) == (B, 3), \
+        "im_info: contiguous [B, 3] float32"
+    return im_info.data_ptr()
+
+
+def stem_fused(data, w256, bias, im_info=None, pixel_means=None):
+    """data [B,3,H,W] fp32/bf16 NCHW -> relu(pool1(relu(conv1 7x7/2 + bias))) as NHWC bf16 [B,Hp,Wp,64] in ONE kernel
+    (csrc/stem.hip:stem_fused_kernel): bit-identical to stem_conv7(relu=True) + stem_bias_relu_pool(zero bias).
+    data [B,H,W,3] uint8 BGR HWC (the canvas of resize_u8): relnet_stem_fused_u8 subtracts `pixel_means` (BGR) inside each image's
+    extent im_info[:, :2] (device [B,3] fp32; None = the whole canvas) and reads 0 outside it -- bit-identical to this function on
+    the fp32 tensor image_transform_u8 makes of the same canvas."""
+    _chk(data, w256, bias)
+    data = data.contiguous()
+    assert w256.shape == (64, 256) and w256.dtype == torch.bfloat16 and bias.dtype == torch.float32
+    if data.dtype == torch.uint8:
+        B, H, W, Cin = data.shape
+        assert Cin == 3 and pixel_means is not None, "uint8 images: [B,H,W,3] BGR HWC and pixel_means"
+        Hp, Wp = _stem_pooled_hw(H, W)
+        out = torch.empty((B, Hp, Wp, 64), device=data.device, dtype=torch.bfloat16)
+        _lib.call('relnet_stem_fused_u8', data.data_ptr(), _im_info_ptr(im_info, B), *_means(pixel_means), w256.data_ptr(),
+                  bias.data_ptr(), out.data_ptr(), B, H, W, _stream())
+        return out
+    B, Cin, H, W = data.shape
+    assert Cin == 3
+    Hp, Wp = _stem_pooled_hw(H, W)
     out = torch.empty((B, Hp, Wp, 64), device=data.device, dtype=torch.bfloat16)
     _lib.call('relnet_stem_fused', data.data_ptr(), _dt(data), w256.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, _stream())
+    return out
+
+
+def image_transform_u8(data, pixel_means, im_info=None, dtype=torch.float32):
+    """data [B,H,W,3] uint8 BGR HWC -> [B,3,H,W] RGB NCHW `dtype` (fp32 / bf16): float(u8 - mean) inside each image's extent
+    im_info[:, :2] (None = the whole canvas), 0 outside -- dataset/image.py:transform + tensor_vstack on the device
+    (relnet_image_transform_u8).  The input of every backbone path that does not run the fused stem."""
+    _chk(data)
+    assert data.dtype == torch.uint8 and data.dim() == 4 and data.shape[3] == 3, "data: [B,H,W,3] uint8"
+    data = data.contiguous()
+    B, H, W, _ = data.shape
+    out = torch.empty((B, 3, H, W), device=data.device, dtype=dtype)
+    _lib.call('relnet_image_transform_u8', data.data_ptr(), _im_info_ptr(im_info, B), *_means(pixel_means), out.data_ptr(),
+              _dt(out), B, H, W, _stream())
+    return out
+
+
+def resize_u8(src, table, scale, canvas_hw):
+    """Batched bilinear resize of uint8 BGR HWC sources (dataset/image.py:resize, bit-identical; relnet_resize_u8).
+    src: flat uint8 device buffer, the B sources back to back; table [B,6] int64 device (byte offset, h, w, flip, nh, nw);
+    scale [B] float64 device (im_scale); canvas_hw (Hc, Wc) host ints.  -> [B,Hc,Wc,3] uint8, each resized image at the top
+    left of its slot (mirrored first where flip != 0), 0 elsewhere.  No host synchronisation."""
+    _chk(src, table, scale)
+    assert src.dtype == torch.uint8 and table.dtype == torch.int64 and scale.dtype == torch.float64
+    table, scale, src = table.contiguous(), scale.contiguous(), src.contiguous()
+    B = table.shape[0]
+    assert tuple(table.shape) == (B, 6) and tuple(scale.shape) == (B,) and B > 0
+    Hc, Wc = int(canvas_hw[0]), int(canvas_hw[1])
+    out = torch.empty((B, Hc, Wc, 3), device=src.device, dtype=torch.uint8)
+    _lib.call('relnet_resize_u8', src.data_ptr(), src.numel(), table.data_ptr(), scale.data_ptr(), out.data_ptr(), B, Hc, Wc,
+              _stream())
     return out
 
 

@@ -117,7 +117,8 @@ class Trainer(object):
         self._frozen_backbone = None
         if getattr(c, 'frozen_on_inference_kernels', True) and torch.device(dev).type == 'cuda':
             from .backbone import Backbone
-            self._frozen_backbone = Backbone(params, dtype=torch.float32 if self.trunk_fp32 else torch.bfloat16, device=dev, fpn=self.fpn, frozen_only=True)
+            self._frozen_backbone = Backbone(params, dtype=torch.float32 if self.trunk_fp32 else torch.bfloat16, device=dev, fpn=self.fpn,
+                                             frozen_only=True, pixel_means=c.pixel_means)
         self.zero_bias64 = torch.zeros(64, device=dev, dtype=torch.float32)
         weights, biases = [], []
         self.bn_scale, self.conv_bias, self.ksize = {}, {}, {'rpn_conv_3x3': 3, 'rpn_out': 1, 'conv_new_1': 1}
@@ -383,16 +384,19 @@ class Trainer(object):
         return ops.conv2d_nhwc(x, w, bias, ksize=self.ksize.get(name, 1), stride=stride, pad=pad, dil=dil, relu=relu,
                                resid=resid, out_dtype=out_dtype)
 
-    def _trunk_forward(self, data, at_conv4=None):
+    def _trunk_forward(self, data, at_conv4=None, im_info=None):
         """Frozen stem + res2, then res3..res5 keeping every ReLU output.  Returns (conv5, conv4, saved units, stage ends).
-        at_conv4(conv4): called once conv4 exists, before res5 is queued (the RPN branch forks there)."""
+        at_conv4(conv4): called once conv4 exists, before res5 is queued (the RPN branch forks there).  data: float NCHW or uint8
+        [B,H,W,3] BGR HWC (Backbone.forward; im_info gives each image's extent)."""
         c = self.cfg
         fb = self._frozen_backbone
         if self.trunk_fp32:
             assert fb is not None
-            x = fb.forward_res2(data)                 # float32 NHWC (Backbone impl 'hip32')
+            x = fb.forward_res2(data, im_info)        # float32 NHWC (Backbone impl 'hip32')
+        elif fb is not None:
+            x = fb.forward_res2(data, im_info)
         else:
-            x = fb.forward_res2(data) if fb is not None else ops.stem_fused(data, self.w_stem, self.b_stem)
+            x = ops.stem_fused(data, self.w_stem, self.b_stem, im_info, c.pixel_means)
         saved = []
         conv4 = None
         ends = {}
@@ -462,7 +466,7 @@ class Trainer(object):
             T.COLSUM_QUEUE = None
 
     def _forward_backward_impl(self, data, im_info, gt_boxes, rpn_label=None, rpn_bbox_target=None, rpn_bbox_weight=None, num_gt=None):
-        """data [B,3,H,W] fp32; gt_boxes [B,G,5]; rpn_label [B, A*h*w] ((a,y,x) order), rpn_bbox_target / weight
+        """data [B,3,H,W] fp32 or [B,H,W,3] uint8 BGR HWC (Backbone.forward); gt_boxes [B,G,5]; rpn_label [B, A*h*w] ((a,y,x) order), rpn_bbox_target / weight
         [B, 4A, h, w] (lib/rpn/rpn.py:assign_anchor layouts) -- or None: computed on the device from gt_boxes
         (`rpn_targets`).  Accumulates gradients into the flat buffers and returns the loss values (reference metric names)."""
         c = self.cfg
@@ -497,7 +501,7 @@ class Trainer(object):
             # the longer of the two branches that meet at ROI pooling
             self._side.wait_stream(main)
             with torch.cuda.stream(self._side):
-                early['t'] = self.rpn_targets(gt_boxes, num_gt, im_info, (_conv4_hw(data.shape[2]), _conv4_hw(data.shape[3])))
+                early['t'] = self.rpn_targets(gt_boxes, num_gt, im_info, tuple(_conv4_hw(n) for n in ops.image_hw(data)))
 
         def rpn_branch(conv4):
             r = self._conv(conv4, 'rpn_conv_3x3', pad=1, relu=True, bias=self.b('rpn_conv_3x3'))
@@ -563,9 +567,9 @@ class Trainer(object):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     rpn_branch(conv4.to(torch.bfloat16))
-            conv5, conv4, saved, _ = self._trunk_forward(data, at_conv4=fork)
+            conv5, conv4, saved, _ = self._trunk_forward(data, at_conv4=fork, im_info=im_info)
         else:
-            conv5, conv4, saved, _ = self._trunk_forward(data)
+            conv5, conv4, saved, _ = self._trunk_forward(data, im_info=im_info)
             rpn_branch(conv4.to(torch.bfloat16))
         # (a float32 trunk -- cfg.trunk_fp32, parity tests -- hands bf16 copies to the bf16 heads and takes their gradients back as float32)
         conv5, conv4 = conv5.to(torch.bfloat16), conv4.to(torch.bfloat16)
@@ -1354,14 +1358,14 @@ class FPNTrainer(Trainer):
         c = self.cfg
         B, N = proposals.shape[:2]
         bt = torch.bfloat16
-        if data.shape[2] % 32 or data.shape[3] % 32:
+        if any(n % 32 for n in ops.image_hw(data)):
             raise ValueError("FPN images must be padded to IMAGE_STRIDE 32, got %s" % (tuple(data.shape),))
         self._grad_buckets().reset()
         self.W.grad.zero_(); self.Bv.grad.zero_()
         self._relayout.run()            # W^T / tap-flipped copies of the current weights for every data-gradient product
         self._fragpack.run()            # ... and the fragment-order copies the chain kernels of the forward read
         out = {}
-        conv5, conv4, saved, ends = self._trunk_forward(data)
+        conv5, conv4, saved, ends = self._trunk_forward(data, im_info=im_info)
         # ---- neck: 1x1 laterals (+bias), nearest 2x upsampling + sum, 3x3 output convs
         src = {32: ends[5], 16: ends[4], 8: ends[3], 4: ends[2]}
         if self.trunk_fp32:             # float32 trunk (parity tests): bf16 copies for the bf16 neck / heads
