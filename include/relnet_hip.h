@@ -76,6 +76,21 @@ int relnet_roi_align_fwd(const void* data, const long* data_strides4, const floa
 int relnet_roi_align_bwd(const void* grad_out, const long* out_strides4, const float* rois, float* grad_in,
                          const long* grad_in_strides4, int R, int C, int H, int W, int PH, int PW, float spatial_scale,
                          int sampling_ratio, int aligned, int batch_index_base, int dtype, void* stream);
+/* ROIAlign over 1..4 maps (FPN levels at 1/4 .. 1/32, or one map with roi_level NULL): roi r pools from level roi_level[r].  Host arrays
+ * of num_levels entries: data_levels / grad_levels (device pointers), strides4_levels [num_levels][4] element strides (b, c, y, x),
+ * heights, widths, spatial_scales.  A row whose batch index (minus batch_index_base) lies outside [0, B) or whose level lies outside
+ * [0, num_levels) pools to zeros and contributes no gradient.  No limit on R beyond the grid's 2^31 - 1 workgroups.  Forward: fp32 / bf16
+ * of any strides, the arithmetic of relnet_roi_align_fwd (bit-identical to it level by level).  Backward: grad_levels fp32, pre-zeroed,
+ * any layout; one workgroup per roi adds its separable patch Wy^T Go Wx (one float atomic per (cell, channel)), the per-sample scatter
+ * for footprints over 64 cells per axis.                                                                                        */
+int relnet_roi_align_levels_fwd(const void* const* data_levels, const long* data_strides4_levels, const int* heights, const int* widths,
+                                const float* spatial_scales, int num_levels, const float* rois, const int* roi_level /*or NULL*/,
+                                void* out, const long* out_strides4, int R, int B, int C, int PH, int PW, int sampling_ratio, int aligned,
+                                int batch_index_base, int dtype, void* stream);
+int relnet_roi_align_levels_bwd(const void* grad_out, const long* out_strides4, const float* rois, const int* roi_level /*or NULL*/,
+                                float* const* grad_levels, const long* grad_strides4_levels, const int* heights, const int* widths,
+                                const float* spatial_scales, int num_levels, int R, int B, int C, int PH, int PW, int sampling_ratio,
+                                int aligned, int batch_index_base, int dtype, void* stream);
 
 /* ---- mx.symbol.ROIPooling(pooled_size=(7,7), spatial_scale=1/16), SYM_REL:252-253 ---------------
  * data/out described by element strides (b|r, c, y, x) so NCHW and channels-last both work.       */

@@ -39,8 +39,9 @@ class Config(object):
     dcn = False               # deformable res5 + DeformablePSROIPooling (symbols/..._dcn_...py)
     dcn_sample_per_part = 4
     dcn_trans_std = 0.1
-    roi_align = False         # True: ROIAlign (ops.roi_align, sampling_ratio 2) feeds fc_new_1 instead of the graphs' ROIPooling -- the operator
-    roi_align_sampling = 2    # north_star names; no reference graph uses it (SYM_REL:252-253 is ROIPooling), so it is off by default
+    roi_align = False         # True: ROIAlign (sampling_ratio 2) feeds fc_new_1 / roi_pool_fc1 instead of the graphs' ROIPooling -- the operator
+    roi_align_sampling = 2    # north_star names; no reference graph uses it (SYM_REL:252-253 is ROIPooling), so it is off by default.  The C4 and
+                              # FPN detectors and trainers honour it; with `dcn` (deformable PSROI pooling) it has no meaning and is refused
     pixel_means = PIXEL_MEANS  # network.PIXEL_MEANS (BGR): subtracted on the device when the detector is given uint8 images
 
     @classmethod
@@ -94,10 +95,18 @@ def fc1_channels_last_perm(c=256, ph=7, pw=7):
     return (ch * (ph * pw) + s).reshape(-1)
 
 
+def check_pooling(cfg):
+    """cfg.roi_align together with cfg.dcn: the DCN graph pools with deformable PSROI pooling (SYM_DCN_RELNMS:1073-1080), there is no
+    ROIAlign in it to switch to -- refused rather than silently ignored."""
+    if getattr(cfg, 'roi_align', False) and getattr(cfg, 'dcn', False):
+        raise ValueError("roi_align and dcn cannot be combined: the DCN graph pools with deformable PSROI pooling")
+
+
 class Detector(object):
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', cfg=None, relation=True,
                  im_hw=(600, 1000), stem='hip'):
         self.cfg = cfg or Config()
+        check_pooling(self.cfg)
         self.dtype, self.device, self.relation, self.im_hw = dtype, device, relation, im_hw
         self.overlap_rpn = True
         # RPN head + proposal beside res5 on a side stream: under hipGraph capture the fork / join are graph edges and it pays from one
@@ -290,8 +299,12 @@ class FPNDetector(object):
         else:
             rois, level, perm, counts = ops.fpn_roi_dispatch(proposals.contiguous())
         N = rois.shape[1]
-        pooled = ops.roi_pool_fpn([f['fpn_ft4'], f['fpn_ft8'], f['fpn_ft16'], f['fpn_ft32']], self.scales,
-                                  rois.view(B * N, 5), level.view(-1), (7, 7), channels_last_out=True)
+        lv = [f['fpn_ft4'], f['fpn_ft8'], f['fpn_ft16'], f['fpn_ft32']]
+        if c.roi_align:
+            pooled = ops.roi_align_fpn(lv, self.scales, rois.view(B * N, 5), level.view(-1), (7, 7), c.roi_align_sampling,
+                                       channels_last_out=True)
+        else:
+            pooled = ops.roi_pool_fpn(lv, self.scales, rois.view(B * N, 5), level.view(-1), (7, 7), channels_last_out=True)
         pooled = pooled.permute(0, 2, 3, 1).reshape(B, N, -1)
         cls_score, bbox_pred, feat = self.head.forward(pooled, rois, key_count=n_rows)
         out = dict(rois=rois, roi_level=level, perm=perm, level_counts=counts, num_rows=n_rows, cls_score=cls_score,

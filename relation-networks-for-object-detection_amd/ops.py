@@ -1035,6 +1035,62 @@ def roi_pool_fpn_bwd(grad_out, argmax, rois, roi_level, level_shapes, batch_inde
     return gins
 
 
+def _level_arrays(ts, scales):
+    import ctypes
+    n = len(ts)
+    return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]), (ctypes.c_long * (4 * n))(*[int(s) for t in ts for s in t.stride()]),
+            (ctypes.c_int * n)(*[int(t.shape[2]) for t in ts]), (ctypes.c_int * n)(*[int(t.shape[3]) for t in ts]),
+            (ctypes.c_float * n)(*[float(x) for x in scales]))
+
+
+def roi_align_fpn(levels, scales, rois, roi_level=None, pooled=(7, 7), sampling_ratio=2, aligned=False, channels_last_out=False,
+                  batch_index_base=0):
+    """ROIAlign over 1..4 maps in one launch (relnet_roi_align_levels_fwd): levels = list of logical [B,C,H_l,W_l] maps (any strides,
+    same B / C / dtype), scales their spatial scales, rois [R,5] fp32, roi_level [R] int32 (None: every roi on levels[0]) -> [R,C,PH,PW]
+    (memory (R,PH,PW,C) when channels_last_out).  Rows with a batch index outside [0, B) or a level outside the list pool to zeros.
+    Per level, bit-identical to roi_align."""
+    import ctypes
+    _chk(rois, roi_level, *levels)
+    assert rois.dtype == torch.float32 and rois.is_contiguous() and len(levels) == len(scales)
+    assert roi_level is None or (roi_level.dtype == torch.int32 and roi_level.is_contiguous() and roi_level.numel() == rois.shape[0])
+    B, Cc = levels[0].shape[:2]
+    dt = levels[0].dtype
+    assert all(t.dtype == dt and t.shape[0] == B and t.shape[1] == Cc for t in levels)
+    R = rois.shape[0]
+    PH, PW = pooled
+    if channels_last_out:
+        out = torch.empty((R, PH, PW, Cc), device=rois.device, dtype=dt).permute(0, 3, 1, 2)
+    else:
+        out = torch.empty((R, Cc, PH, PW), device=rois.device, dtype=dt)
+    ptrs, strides, hs, ws, sc = _level_arrays(levels, scales)
+    _lib.call('relnet_roi_align_levels_fwd', ctypes.addressof(ptrs), ctypes.addressof(strides), ctypes.addressof(hs), ctypes.addressof(ws),
+              ctypes.addressof(sc), len(levels), rois.data_ptr(), _ptr(roi_level), out.data_ptr(), _strides4(out), R, B, Cc, PH, PW,
+              int(sampling_ratio), int(bool(aligned)), batch_index_base, _dt(levels[0]), _stream())
+    return out
+
+
+def roi_align_fpn_bwd(grad_out, rois, roi_level, level_shapes, scales, sampling_ratio=2, aligned=False, batch_index_base=0,
+                      channels_last=False):
+    """Adjoint of roi_align_fpn: grad_out logical [R,C,PH,PW] (any strides, fp32 / bf16), level_shapes = [(B,C,H_l,W_l)] -> list of fp32
+    gradients, logical [B,C,H_l,W_l] (memory NCHW, or NHWC with channels_last: `.permute(0, 2, 3, 1)` is then contiguous)."""
+    import ctypes
+    _chk(grad_out, rois, roi_level)
+    assert rois.dtype == torch.float32 and rois.is_contiguous() and len(level_shapes) == len(scales)
+    assert roi_level is None or (roi_level.dtype == torch.int32 and roi_level.is_contiguous() and roi_level.numel() == rois.shape[0])
+    R, Cc, PH, PW = grad_out.shape
+    if channels_last:
+        gins = [torch.zeros((sh[0], sh[2], sh[3], sh[1]), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2) for sh in level_shapes]
+    else:
+        gins = [torch.zeros(tuple(sh), device=grad_out.device, dtype=torch.float32) for sh in level_shapes]
+    assert all(t.shape[0] == gins[0].shape[0] and t.shape[1] == Cc for t in gins)
+    ptrs, strides, hs, ws, sc = _level_arrays(gins, scales)
+    _lib.call('relnet_roi_align_levels_bwd', grad_out.data_ptr(), _strides4(grad_out), rois.data_ptr(), _ptr(roi_level),
+              ctypes.addressof(ptrs), ctypes.addressof(strides), ctypes.addressof(hs), ctypes.addressof(ws), ctypes.addressof(sc),
+              len(gins), R, gins[0].shape[0], Cc, PH, PW, int(sampling_ratio), int(bool(aligned)), batch_index_base, _dt(grad_out),
+              _stream())
+    return gins
+
+
 def upsample2x_add_(lateral, top):
     """lateral [B,H,W,C] += nearest-upsampled top [B,H/2,W/2,C] (both NHWC contiguous), in place."""
     _chk(lateral, top)

@@ -30,7 +30,7 @@ from . import ops, losses, train_ops as T
 from . import dist as D
 from .backbone import unit_names, conv_bn_names, fold_bn, EPS
 from .relation import attention_module_backward, _module_forward, pack_pair_pos, GradSink
-from .detector import Config, fc1_channels_last_perm
+from .detector import Config, fc1_channels_last_perm, check_pooling
 from .operator_py.proposal import generate_anchors, propose_batch
 
 
@@ -88,6 +88,7 @@ class _Flat(object):
 class Trainer(object):
     def __init__(self, params, cfg=None, device='cuda', im_hw=(600, 1000)):
         self.cfg = cfg or TrainConfig()
+        check_pooling(self.cfg)
         self.device, self.im_hw = device, im_hw
         c = self.cfg
         dev = device
@@ -603,6 +604,9 @@ class Trainer(object):
             pooled = ops.deformable_psroi_pool(nchw(feat), r5, trans, sc_, feat.shape[3], 1, 7, 7, c.dcn_sample_per_part,
                                                c.dcn_trans_std, False, channels_last_out=True)
             argmax = None
+        elif c.roi_align:           # one map, no level table: the single-map case of the levels kernels
+            pooled = ops.roi_align_fpn([nchw(feat)], [1.0 / c.feat_stride], r5, None, (7, 7), c.roi_align_sampling, channels_last_out=True)
+            argmax = None
         else:
             pooled, argmax = ops.roi_pool(nchw(feat), r5, (7, 7), 1.0 / c.feat_stride, channels_last_out=True, want_argmax=True)
         pooled2 = pooled.permute(0, 2, 3, 1).reshape(B * R, -1)
@@ -615,7 +619,7 @@ class Trainer(object):
             out['bbox_target'], out['bbox_weight'] = bbox_target, weights_ohem
             out['bbox_pred'], out['cls_score'], out['fc_all_2_relu'] = bbox_pred, cls_score, x2
             return out
-        # ROIPooling backward -> gradient of conv_new_1_relu
+        # ROIPooling / ROIAlign backward -> gradient of conv_new_1_relu
         if c.dcn:
             gp = d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2)
             gd1, gtrans = ops.deformable_psroi_pool_bwd(gp, nchw(feat), r5, trans, sc_, feat.shape[3], 1, 7, 7,
@@ -625,6 +629,11 @@ class Trainer(object):
             gd2, _ = ops.deformable_psroi_pool_bwd(d_t0.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), nchw(feat), r5, None, sc_,
                                                    feat.shape[3], 1, 7, 7, c.dcn_sample_per_part, 0.0, True)
             d_feat = (gd1 + gd2).permute(0, 2, 3, 1).to(bt).contiguous()       # logical NCHW stored NHWC -> NHWC bf16
+        elif c.roi_align:
+            d_feat, = ops.roi_align_fpn_bwd(d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), r5, None,
+                                            [(B, feat.shape[3], feat.shape[1], feat.shape[2])], [1.0 / c.feat_stride], c.roi_align_sampling,
+                                            channels_last=True)
+            d_feat = d_feat.permute(0, 2, 3, 1).to(bt)          # NHWC memory already: one conversion pass
         else:
             d_feat = ops.roi_pool_bwd(d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), argmax, r5,
                                       (B, feat.shape[3], feat.shape[1], feat.shape[2]), channels_last=True)
@@ -1392,15 +1401,24 @@ class FPNTrainer(Trainer):
         label, bbox_target, bbox_weight = gat(label), gat(bbox_target).contiguous(), gat(bbox_weight).contiguous()
         nchw = lambda t: t.permute(0, 3, 1, 2)
         lv = [nchw(feats[4]), nchw(feats[8]), nchw(feats[16]), nchw(feats[32])]
-        pooled, argmax = ops.roi_pool_fpn(lv, self.scales, rois_s.view(B * R, 5), level.view(-1), (7, 7), channels_last_out=True,
-                                          want_argmax=True)
+        if c.roi_align:
+            pooled = ops.roi_align_fpn(lv, self.scales, rois_s.view(B * R, 5), level.view(-1), (7, 7), c.roi_align_sampling,
+                                       channels_last_out=True)
+        else:
+            pooled, argmax = ops.roi_pool_fpn(lv, self.scales, rois_s.view(B * R, 5), level.view(-1), (7, 7), channels_last_out=True,
+                                              want_argmax=True)
         pooled2 = pooled.permute(0, 2, 3, 1).reshape(B * R, -1)
         d_pool, hs = self._head_forward_backward(pooled2, rois_s, N, label.contiguous(), bbox_target, bbox_weight, im_info,
                                                  gt_boxes, num_gt, out, key_count=key_count)
         x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem = hs
         # ---- pooling backward into the four pyramid maps
-        g_lv = ops.roi_pool_fpn_bwd(d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), argmax, rois_s.view(B * R, 5), level.view(-1),
-                                    [tuple(t.shape) for t in lv], channels_last=True)
+        d_pool4 = d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2)
+        if c.roi_align:
+            g_lv = ops.roi_align_fpn_bwd(d_pool4, rois_s.view(B * R, 5), level.view(-1), [tuple(t.shape) for t in lv], self.scales,
+                                         c.roi_align_sampling, channels_last=True)
+        else:
+            g_lv = ops.roi_pool_fpn_bwd(d_pool4, argmax, rois_s.view(B * R, 5), level.view(-1), [tuple(t.shape) for t in lv],
+                                        channels_last=True)
         d_feats = {lvl: g.permute(0, 2, 3, 1).to(bt) for lvl, g in zip((4, 8, 16, 32), g_lv)}
         # ---- neck backward (top-down pathway reversed: finest level first, gradients flow up to the coarser tops)
         d_tops, inject, d_c5 = {}, {}, None
