@@ -1269,10 +1269,12 @@ def lnms_scatter_bwd(d_sorted, rank_idx, N):
 class WgradQueue(object):
     """Weight-gradient products collected for ONE grouped launch (csrc/wgrad.hip: stream-K over the (layer, tile, slab) units
     of all queued layers).  `add` has the signature of `wgrad_tn`; `flush` launches what is queued.  The queue keeps the
-    operand tensors alive until the launch has been issued (stream order does the rest)."""
+    operand tensors alive until the launch has been issued (stream order does the rest).  The operands must not be modified in
+    place before the flush: `flush` checks their version counters before anything is launched (not `out`'s: a view of the flat
+    gradient buffer shares its counter with the other slices, which are written while products are queued)."""
 
     def __init__(self):
-        self.items, self.keep = [], []
+        self.items, self.keep, self.versions = [], [], []
 
     def add(self, dy2d, x, out, row_scale=None, cout=None, conv=None):
         _chk(dy2d, x, out, row_scale)
@@ -1300,6 +1302,7 @@ class WgradQueue(object):
                            _ptr(row_scale) or None, P, cout, cin, ks, stride, dil, pad, B, Ho, Wo, Hin, Win)
         self.items.append(d)
         self.keep.append((dy2d, x, out, row_scale))
+        self.versions.append([t._version for t in (dy2d, x, row_scale) if t is not None])
 
     def __len__(self):
         return len(self.items)
@@ -1310,9 +1313,14 @@ class WgradQueue(object):
         n = len(self.items)
         if n == 0:
             return
-        arr = (_lib.WgradDesc * n)(*self.items)
+        items, keep, versions = self.items, self.keep, self.versions
+        self.items, self.keep, self.versions = [], [], []
+        for (dy2d, x, _, row_scale), v in zip(keep, versions):
+            assert [t._version for t in (dy2d, x, row_scale) if t is not None] == v, \
+                "an operand of a queued weight-gradient product %s was modified in place before the flush" % (tuple(dy2d.shape),)
+        arr = (_lib.WgradDesc * n)(*items)
         lib = _lib.load()
-        ws = torch.empty(int(lib.relnet_wgrad_workspace_bytes(n)), device=self.keep[0][0].device, dtype=torch.uint8)
+        ws = torch.empty(int(lib.relnet_wgrad_workspace_bytes(n)), device=keep[0][0].device, dtype=torch.uint8)
         import ctypes
         if workgroups:
             lib.relnet_wgrad_tune(int(workgroups), 0, 0)
@@ -1321,7 +1329,6 @@ class WgradQueue(object):
         finally:
             if workgroups:
                 lib.relnet_wgrad_tune(0, 0, 0)
-        self.items, self.keep = [], []
         return ws          # the caller may hold on to it; stream order already protects it from reuse on this stream
 
 

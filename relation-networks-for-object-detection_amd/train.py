@@ -21,8 +21,6 @@ MI355X-first choices:
     recomputed from their inputs instead of storing [16, N, M] maps.
 """
 
-import os
-
 import numpy as np
 import torch
 
@@ -48,6 +46,20 @@ class TrainConfig(Config):
     relation = True               # two relation modules in the 2FC head (False: the plain head of resnet_v1_101_rcnn_learn_nms_1024_...)
     enable_ohem = True            # TRAIN.ENABLE_OHEM (False: SoftmaxOutput over all rois, bbox loss scaled by 1 / 300)
     fixed_params = None           # network.FIXED_PARAMS of the experiment file (None: dist.FIXED_PARAMS, the end2end yamls' list)
+
+
+# workgroups of the RPN head's grouped weight-gradient launch on the side stream: a quarter of the chip, the head's kernels beside it keep
+# theirs (same box, 8 images: 16.99 ms per step with these products in the heads bucket's launch on the main stream, 16.92 on 32 workgroups,
+# 16.87 - 16.89 on 64, 16.99 on 128)
+RPN_WGRAD_WORKGROUPS = 64
+
+
+def conv4_hw(h, w):
+    """Spatial size of conv4 (stride 16) for an h x w image: the stem's pooled map (conv1 7x7 / 2, pool1 3x3 / 2), then the stride-2
+    res3a and res4a."""
+    half = lambda n: (n - 1) // 2 + 1
+    hp, wp = ops._stem_pooled_hw(h, w)
+    return half(half(hp)), half(half(wp))
 
 
 def all_reduce_sum(*buffers):
@@ -108,34 +120,23 @@ class Trainer(object):
         # kept on the host under the reference's names so that a checkpoint holds the complete arg / aux dictionaries
         self._fixed_src = {k: torch.as_tensor(v).detach().to('cpu', torch.float32).clone() for k, v in params.items()
                            if ('moving_' in k) or not D.is_trainable(k)}
-        # ---- frozen part (conv1, res2): the inference kernels with folded BN
-        self.frozen = {}
-        w1, b1 = fold_bn(params['conv1_weight'], params['bn_conv1_gamma'], params['bn_conv1_beta'],
-                         params['bn_conv1_moving_mean'], params['bn_conv1_moving_var'])
-        self.w_stem, self.b_stem = ops.pack_stem_weight(w1, torch.bfloat16, dev), f32(b1)
-        # conv1 + res2 never change: they run on the inference kernels (fused stem, halo 3x3, chain kernels) of a Backbone built from the
-        # same parameters (cfg.frozen_on_inference_kernels = False keeps the per-layer convolution launches)
-        self._frozen_backbone = None
-        if getattr(c, 'frozen_on_inference_kernels', True) and torch.device(dev).type == 'cuda':
-            from .backbone import Backbone
-            self._frozen_backbone = Backbone(params, dtype=torch.float32 if self.trunk_fp32 else torch.bfloat16, device=dev, fpn=self.fpn,
-                                             frozen_only=True, pixel_means=c.pixel_means)
-        self.zero_bias64 = torch.zeros(64, device=dev, dtype=torch.float32)
+        # ---- frozen part: conv1 + res2 never change; they run on the inference kernels (fused stem, halo 3x3, chain kernels) of a
+        # Backbone built from the same parameters with folded BN
+        from .backbone import Backbone
+        self._frozen_backbone = Backbone(params, dtype=torch.float32 if self.trunk_fp32 else torch.bfloat16, device=dev, fpn=self.fpn,
+                                         frozen_only=True, pixel_means=c.pixel_means)
         weights, biases = [], []
         self.bn_scale, self.conv_bias, self.ksize = {}, {}, {'rpn_conv_3x3': 3, 'rpn_out': 1, 'conv_new_1': 1}
         for conv, bn, oc, ic, k in conv_bn_names():
-            if conv == 'conv1':
+            if conv == 'conv1' or conv.startswith('res2'):
                 continue
             w, b = fold_bn(params[conv + '_weight'], params[bn + '_gamma'], params[bn + '_beta'],
                            params[bn + '_moving_mean'], params[bn + '_moving_var'])
             self.ksize[conv] = k
             self.conv_bias[conv] = f32(b)                                   # beta - mean * s: frozen
-            if conv.startswith('res2'):
-                self.frozen[conv] = ops.pack_conv_weight(w, torch.bfloat16, dev)
-            else:
-                s = (params[bn + '_gamma'].double() / torch.sqrt(params[bn + '_moving_var'].double() + EPS)).float()
-                self.bn_scale[conv] = f32(s)
-                weights.append((conv, w.permute(0, 2, 3, 1).reshape(oc, -1)))
+            s = (params[bn + '_gamma'].double() / torch.sqrt(params[bn + '_moving_var'].double() + EPS)).float()
+            self.bn_scale[conv] = f32(s)
+            weights.append((conv, w.permute(0, 2, 3, 1).reshape(oc, -1)))
         # ---- RPN head, conv_new_1, 2FC head, relation modules
         def conv_w(name):
             w = params[name + '_weight']
@@ -209,19 +210,13 @@ class Trainer(object):
         self.anchors = torch.as_tensor(self.anchors_host, dtype=torch.float64, device=dev)
         self.step_count = 0
         # state that used to be created on first use -- inside a hipGraph capture that turned into a captured fill / mid-capture
-        # stream and attribute calls: the device step counter of the anchor sampler, the RPN side stream, the queue of
-        # weight-gradient products
+        # stream and attribute calls: the device step counter of the anchor sampler, the RPN side stream, the queues of
+        # the deferred gradient work -- weight-gradient products and bias-gradient column sums, each launched grouped when a gradient
+        # bucket completes (`_flush_wgrads`)
         self._anchor_step = torch.zeros(1, device=dev, dtype=torch.int64)
-        self._side = torch.cuda.Stream(device=dev) if torch.cuda.is_available() and torch.device(dev).type == 'cuda' else None
+        self._side = torch.cuda.Stream(device=dev)
         self._wq = ops.WgradQueue()
-        # bias-gradient column sums of a gradient bucket in one grouped launch (train_ops.ColsumQueue; cfg.colsum_grouped / RELNET_COLSUM_GROUP=0: one launch each)
         self._cq = T.ColsumQueue()
-        # parameter-only gradient work (the relation modules' geometry backward) on a side stream beside the data-gradient chain, joined before the
-        # bucket is announced: OPT-IN (cfg.aux_stream / RELNET_AUX_STREAM=1).  Measured, same box, r06: 6.95 -> 7.16-7.67 ms at one image, 17.93 -> 18.02-18.12 ms
-        # at 8 -- like the weight-gradient side stream, every fork / join inside the captured step costs more than the overlap returns
-        self._aux = torch.cuda.Stream(device=dev) if (self._side is not None and getattr(c, 'aux_stream', os.environ.get('RELNET_AUX_STREAM', '0') != '0')) else None
-        self._aux_keep, self._aux_pending = [], False
-        self._colsum_grouped = bool(getattr(c, 'colsum_grouped', os.environ.get('RELNET_COLSUM_GROUP', '1') != '0'))
         # every data-parallel rank samples its own fg / bg anchor subsets (cfg.rank_in_anchor_seed = False: the same subsets on every
         # rank, what the two-rank gradient-sum check needs)
         self._rank, self._world = (0, 1) if not getattr(c, 'rank_in_anchor_seed', True) else ((torch.distributed.get_rank(), torch.distributed.get_world_size())
@@ -251,10 +246,10 @@ class Trainer(object):
         # ---- res3 .. res5 block boundaries on the inference chain kernels (csrc/bottleneck.hip): expand + shortcut + ReLU of unit u
         # and reduce + ReLU of unit u + 1 in one launch.  They read the weights in MFMA-fragment order; the trained weights change every
         # step, so ONE grouped launch per step (ops.FragRepack) rewrites those copies next to the data-gradient layouts above.
-        # cfg.train_chain = False keeps the per-layer convolution launches (the round-4 form).
+        # (The float32 trunk keeps the per-layer convolution launches.)
         self._fragpack = ops.FragRepack(dev)
         self.chain_units = {}                               # unit -> (has_next_reduce, next unit)
-        if getattr(c, 'train_chain', os.environ.get('RELNET_TRAIN_CHAIN', '1') != '0') and torch.device(dev).type == 'cuda' and not self.trunk_fp32:
+        if not self.trunk_fp32:
             trainable = [u for u in self.units if u[0] >= 3]
             for (st, nm, ic, mc, oc, stride, dil, proj), nxt in zip(trainable, trainable[1:] + [None]):
                 if c.dcn and st == 5:
@@ -268,16 +263,8 @@ class Trainer(object):
                 self.chain_units[nm] = (with_reduce, nxt[1] if with_reduce else None)
             self._fragpack.build()
         # data gradient through `relu(expand + shortcut)` with the ReLU mask in the GEMM epilogue (relnet_gemm_nt_mask) instead of a
-        # separate relnet_relu_bwd pass over three [pixels, 4 mid] maps per unit
-        self.mask_epilogue = getattr(c, 'mask_epilogue', os.environ.get('RELNET_TRAIN_MASK_EPI', '1') != '0') and not self.trunk_fp32
-        # weight-gradient products of the trunk launched on a side stream every `wgrad_overlap` units (0, the default: one grouped
-        # launch per gradient bucket on the main stream): built to let the persistent stream-K kernel fill the CUs that the
-        # data-gradient GEMMs of a 19 152-pixel map leave idle.  Measured (r05, same box, 8 images, ms per step): off 20.27, every
-        # 8 units 20.37, 4: 20.52, 2: 20.95, 1: 21.71 -- the co-resident workgroups slow the GEMMs by more than the overlap returns
-        # and smaller groups lose stream-K efficiency; kept as a knob (cfg.wgrad_overlap / RELNET_WGRAD_OVERLAP)
-        self.wgrad_overlap = int(getattr(c, 'wgrad_overlap', os.environ.get('RELNET_WGRAD_OVERLAP', '0')))
-        self._wgrad_side = torch.cuda.Stream(device=dev) if (self.wgrad_overlap > 0 and self._side is not None) else None
-        self._wgrad_keep, self._wgrad_pending = [], False
+        # separate relnet_relu_bwd pass over three [pixels, 4 mid] maps per unit (off for the float32 trunk)
+        self.mask_epilogue = not self.trunk_fp32
         self._scratch_bufs = {}
 
     # ---- accessors ----------------------------------------------------------------------------------------
@@ -320,48 +307,12 @@ class Trainer(object):
         g = self.W.view(self.W.grad, name)
         return g.view(g.shape[0], -1), scale_rows, self._wq       # the products wait there for ONE grouped stream-K launch per gradient bucket
 
-    def _flush_wgrads(self, final=True):
-        """Launch the queued weight-gradient products (csrc/wgrad.hip, one grouped launch).  With a weight-gradient side stream the
-        launch goes there (fork: side waits for everything queued on the current stream); final=True also joins -- the current stream
-        waits for every product launched on the side stream since the last join (a gradient bucket is complete only then).  The
-        operand tensors stay referenced until the join: their blocks must not be handed out again on the main stream while the
-        side stream still reads them."""
-        self._cq.flush()             # the queued bias-gradient column sums: one grouped launch
-        if self._aux_pending:        # deferred parameter-gradient work: the bucket is complete only once it has run
-            torch.cuda.current_stream().wait_stream(self._aux)
-            self._aux_pending, self._aux_keep = False, []
-        side = self._wgrad_side
-        if side is None:
-            self._wq.flush()
-            return
-        main = torch.cuda.current_stream()
-        if len(self._wq):
-            side.wait_stream(main)
-            self._wgrad_keep.append(list(self._wq.keep))
-            with torch.cuda.stream(side):
-                self._wgrad_keep.append(self._wq.flush(workgroups=int(os.environ.get('RELNET_WGRAD_SIDE_WGS', '0'))))
-            self._wgrad_pending = True
-        if final and self._wgrad_pending:
-            main.wait_stream(side)
-            self._wgrad_pending = False
-            self._wgrad_keep = []
-
-    def _defer(self, fn, keep):
-        """Run fn() on the auxiliary stream after everything queued so far (GradSink.defer); joined in _flush_wgrads.  `keep`: the tensors fn
-        reads -- referenced until the join, and marked as used on that stream for the caching allocator (outside a capture)."""
-        if self._aux is None:
-            fn()
-            return
-        main = torch.cuda.current_stream()
-        self._aux.wait_stream(main)
-        with torch.cuda.stream(self._aux):
-            fn()
-        if not torch.cuda.is_current_stream_capturing():
-            for t in keep:
-                if torch.is_tensor(t) and t.is_cuda:
-                    t.record_stream(self._aux)
-        self._aux_keep.append(keep)
-        self._aux_pending = True
+    def _flush_wgrads(self):
+        """Launch the deferred gradient work of the step so far, on the current stream: the queued bias-gradient column sums
+        (relnet_colsum_add_grouped) and weight-gradient products (csrc/wgrad.hip), one grouped launch each.  A gradient bucket is
+        complete only after this."""
+        self._cq.flush()
+        self._wq.flush()
 
     def _scratch(self, name, shape, dtype):
         """Persistent zero-initialised work buffer (created on first use, i.e. in the eager warm-up step, never inside a capture)."""
@@ -375,14 +326,14 @@ class Trainer(object):
             self.Bv.view(self.Bv.grad, name).add_(db.reshape(-1))
 
     def _bg(self, name):
-        """fp32 view of `name`'s slice of the flat bias-gradient buffer: the target T.colsum_add / linear_bwd(bgrad_to=) accumulate into."""
-        return self.Bv.view(self.Bv.grad, name).view(-1)
+        """(fp32 view of `name`'s slice of the flat bias-gradient buffer, the step's ColsumQueue): the bias target T.colsum_add(x, *target) /
+        linear_bwd(bgrad_to=) / relation.GradSink accumulate into, with the column sums waiting for the bucket's grouped launch."""
+        return self.Bv.view(self.Bv.grad, name).view(-1), self._cq
 
     # ---- forward -------------------------------------------------------------------------------------------
-    def _conv(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None, bias=None, out_dtype=None, w=None):
-        w = self.w(name) if w is None else w
+    def _conv(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None, bias=None, out_dtype=None):
         bias = self.conv_bias[name] if bias is None else bias
-        return ops.conv2d_nhwc(x, w, bias, ksize=self.ksize.get(name, 1), stride=stride, pad=pad, dil=dil, relu=relu,
+        return ops.conv2d_nhwc(x, self.w(name), bias, ksize=self.ksize.get(name, 1), stride=stride, pad=pad, dil=dil, relu=relu,
                                resid=resid, out_dtype=out_dtype)
 
     def _trunk_forward(self, data, at_conv4=None, im_info=None):
@@ -390,14 +341,7 @@ class Trainer(object):
         at_conv4(conv4): called once conv4 exists, before res5 is queued (the RPN branch forks there).  data: float NCHW or uint8
         [B,H,W,3] BGR HWC (Backbone.forward; im_info gives each image's extent)."""
         c = self.cfg
-        fb = self._frozen_backbone
-        if self.trunk_fp32:
-            assert fb is not None
-            x = fb.forward_res2(data, im_info)        # float32 NHWC (Backbone impl 'hip32')
-        elif fb is not None:
-            x = fb.forward_res2(data, im_info)
-        else:
-            x = ops.stem_fused(data, self.w_stem, self.b_stem, im_info, c.pixel_means)
+        x = self._frozen_backbone.forward_res2(data, im_info)      # (float32 NHWC for the float32 trunk: Backbone impl 'hip32')
         saved = []
         conv4 = None
         ends = {}
@@ -410,15 +354,8 @@ class Trainer(object):
                     at_conv4(conv4)
             if proj and stage > 2:
                 ends[stage - 1] = x
-            if stage == 2 and fb is not None:
-                continue                   # (ran inside forward_res2)
             if stage == 2:
-                fw = lambda n: self.frozen[n]
-                sc = self._conv(x, n1, stride=stride, w=fw(n1)) if proj else x
-                y = self._conv(x, na, stride=stride, relu=True, w=fw(na))
-                y = self._conv(y, nb, pad=dil, dil=dil, relu=True, w=fw(nb))
-                x = self._conv(y, nc, relu=True, resid=sc, w=fw(nc))
-                continue
+                continue                   # (ran inside forward_res2)
             sc = self._conv(x, n1, stride=stride) if proj else x
             y1 = y_pre if y_pre is not None else self._conv(x, na, stride=stride, relu=True)
             y_pre = None
@@ -458,13 +395,11 @@ class Trainer(object):
 
     def forward_backward(self, *args, **kwargs):
         """One forward + backward pass (arguments: see `_forward_backward_impl` of the trainer class).  While it runs, bias-gradient column sums
-        are queued (train_ops.COLSUM_QUEUE) and launched grouped when a gradient bucket completes (`_flush_wgrads`)."""
-        T.COLSUM_QUEUE = self._cq if self._colsum_grouped else None
+        and weight-gradient products are queued on the trainer and launched grouped when a gradient bucket completes (`_flush_wgrads`)."""
         try:
             return self._forward_backward_impl(*args, **kwargs)
         finally:
-            self._cq.flush()            # (nothing is left unless a caller skipped the bucket announcements)
-            T.COLSUM_QUEUE = None
+            self._flush_wgrads()        # (nothing is left unless a caller skipped the bucket announcements)
 
     def _forward_backward_impl(self, data, im_info, gt_boxes, rpn_label=None, rpn_bbox_target=None, rpn_bbox_weight=None, num_gt=None):
         """data [B,3,H,W] fp32 or [B,H,W,3] uint8 BGR HWC (Backbone.forward); gt_boxes [B,G,5]; rpn_label [B, A*h*w] ((a,y,x) order), rpn_bbox_target / weight
@@ -474,46 +409,35 @@ class Trainer(object):
         B = data.shape[0]
         self._grad_buckets().reset()
         self.W.grad.zero_(); self.Bv.grad.zero_()
-        # W^T / tap-flipped copies of the current weights for every data-gradient product: only the BACKWARD reads them.  With the RPN branch on
-        # its side stream they are made after conv_new_1, where the main stream otherwise waits for the proposals (one image: the branch's
-        # single-workgroup sort / NMS kernels are the longer path and leave the chip idle); otherwise here
-        late_relayout = (self._side is not None and getattr(self, 'overlap_rpn', os.environ.get('RELNET_TRAIN_OVERLAP', '1') != '0')
-                         and os.environ.get('RELNET_LATE_RELAYOUT', '1') != '0')
-        if not late_relayout:
-            self._relayout.run()
         self._fragpack.run()            # the fragment-order copies the chain kernels of the forward read
         # The RPN branch (head convolutions, anchor targets, losses, proposals, proposal targets: everything that hangs off conv4)
         # runs on a side stream BESIDE res5 / conv_new_1 -- its top-k / sort / NMS / target kernels are one workgroup per image and
         # leave the GPU idle on their own; fork when conv4 exists, join before ROI pooling (graph edges under capture).
         out = {}
         br = {}
-        main = torch.cuda.current_stream()
+        main, side = torch.cuda.current_stream(), self._side
         nchw = lambda t: t.permute(0, 3, 1, 2)
+        # the RPN head's backward runs on the side stream too (not in a learn-NMS-only step: nothing behind that head is differentiated)
+        rpn_bwd_side = not self.lnms_only
 
-        def _conv4_hw(n):                  # spatial size of conv4 (stride 16): conv1 7x7 / 2 pad 3, pool1 3x3 / 2 (ceil), res3a and res4a stride 2
-            n = (n + 2 * 3 - 7) // 2 + 1
-            n = -(-(n - 3) // 2) + 1
-            n = (n - 1) // 2 + 1
-            return (n - 1) // 2 + 1
-        early = {}
-        if rpn_label is None and getattr(self, 'overlap_rpn', os.environ.get('RELNET_TRAIN_OVERLAP', '1') != '0') and self._side is not None:
+        early = None
+        if rpn_label is None:
             # the anchor targets depend on the ground truth only (lib/rpn/rpn.py:assign_anchor runs in the LOADER in the reference): on the side stream
             # from the very start of the step, beside the stem -- their 0.23 ms (8 images) used to sit between the RPN head and the proposals, on
             # the longer of the two branches that meet at ROI pooling
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                early['t'] = self.rpn_targets(gt_boxes, num_gt, im_info, tuple(_conv4_hw(n) for n in ops.image_hw(data)))
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                early = self.rpn_targets(gt_boxes, num_gt, im_info, conv4_hw(*ops.image_hw(data)))
 
         def rpn_branch(conv4):
             r = self._conv(conv4, 'rpn_conv_3x3', pad=1, relu=True, bias=self.b('rpn_conv_3x3'))
             rpn = self._conv(r, 'rpn_out', bias=self.b('rpn_out'), out_dtype=torch.float32)             # [B,h,w,72]
             h, wd_ = rpn.shape[1], rpn.shape[2]
             na2 = self.na2
-            lbl, tgt_in, wgt_in = rpn_label, rpn_bbox_target, rpn_bbox_weight
-            if lbl is None and early.get('t') is not None and tuple(early['t'][1].shape[2:]) == (h, wd_):
-                lbl, tgt_in, wgt_in = early['t']           # (computed on this stream at the start of the step)
-            elif lbl is None:
-                lbl, tgt_in, wgt_in = self.rpn_targets(gt_boxes, num_gt, im_info, (h, wd_))
+            lbl, tgt_in, wgt_in = (rpn_label, rpn_bbox_target, rpn_bbox_weight) if early is None else early
+            if early is not None and tuple(tgt_in.shape[2:]) != (h, wd_):
+                # (never recomputed here: that would advance the anchor sampler's device step counter a second time in this step)
+                raise RuntimeError("early RPN anchor targets are %dx%d, conv4 is %dx%d" % (tgt_in.shape[2], tgt_in.shape[3], h, wd_))
             # -- RPN losses (per image, like one image per device in the reference)
             score_nchw = rpn[..., :na2].permute(0, 3, 1, 2).contiguous()                                 # [B,2A,h,w]
             # per-image 'valid' normalisation (one image per executor in the reference) in ONE launch: group = one image's anchors
@@ -537,63 +461,45 @@ class Trainer(object):
             if rpn_bwd_side:
                 br['ev'] = torch.cuda.Event()
                 br['ev'].record()               # main resumes here (rois and their targets exist); the RPN head's backward follows on this stream
-                if late_relayout:
-                    br['bwd'] = (conv4, r, d_rpn)     # ... once the main stream has made the weight copies it reads (enqueued below)
-                else:
-                    rpn_backward(conv4, r, d_rpn)
+                br['bwd'] = (conv4, r, d_rpn)   # ... once the main stream has made the weight copies it reads (enqueued below)
 
         def rpn_backward(conv4, r, d_rpn):
-            # RPN head backward (joins the trunk at conv4).  It depends on the RPN losses only: with the branch on its side stream it runs there,
-            # beside ROI pooling / the 2FC head / the learn-NMS branch (launches of <= 150 workgroups), and with it the two RPN weight gradients as
-            # their own grouped launch on 64 workgroups (a quarter of the chip: the head's kernels beside it keep theirs);
-            # RELNET_RPN_WGRAD_SIDE=0 leaves those in the 'heads' bucket's launch on the main stream
-            nwg = int(os.environ.get('RELNET_RPN_WGRAD_SIDE', '64')) if rpn_bwd_side else 0
-            rq = ops.WgradQueue() if nwg else None
-            wg = (lambda n: self._wg(n)[:2] + (rq,)) if nwg else self._wg
+            # RPN head backward (joins the trunk at conv4), on the side stream beside ROI pooling / the 2FC head / the learn-NMS branch (launches of
+            # <= 150 workgroups), and with it the two RPN weight gradients as their own grouped launch on RPN_WGRAD_WORKGROUPS workgroups
+            rq = ops.WgradQueue()
+            wg = lambda n: self._wg(n)[:2] + (rq,)
             g_r, dw = T.conv1x1_bwd(r, self.w('rpn_out'), d_rpn, w_t=self.wt('rpn_out'), keep_splits=True, wgrad_to=wg('rpn_out'), relu_mask=r)
-            T.colsum_add(d_rpn, self._bg('rpn_out'))
+            T.colsum_add(d_rpn, *self._bg('rpn_out'))
             d_conv4_rpn, dw = T.conv3x3_bwd(conv4, self._dgrad_w('rpn_conv_3x3', 512), g_r, dil=1, keep_splits=True, wgrad_to=wg('rpn_conv_3x3'))
-            T.colsum_add(g_r, self._bg('rpn_conv_3x3'))
-            br.update(g_r=g_r, d_conv4_rpn=d_conv4_rpn)
-            if nwg:
-                br['rq_keep'] = rq.flush(workgroups=nwg)
+            T.colsum_add(g_r, *self._bg('rpn_conv_3x3'))
+            br.update(g_r=g_r, d_conv4_rpn=d_conv4_rpn, rq_keep=rq.flush(workgroups=RPN_WGRAD_WORKGROUPS))
 
-        rpn_bwd_side = False
-        side = None
-        if getattr(self, 'overlap_rpn', os.environ.get('RELNET_TRAIN_OVERLAP', '1') != '0'):
-            side = self._side
-            rpn_bwd_side = os.environ.get('RELNET_RPN_BWD_SIDE', '1') != '0' and not self.lnms_only
-
-            def fork(conv4):
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    rpn_branch(conv4.to(torch.bfloat16))
-            conv5, conv4, saved, _ = self._trunk_forward(data, at_conv4=fork, im_info=im_info)
-        else:
-            conv5, conv4, saved, _ = self._trunk_forward(data, im_info=im_info)
-            rpn_branch(conv4.to(torch.bfloat16))
+        def fork(conv4):
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                rpn_branch(conv4.to(torch.bfloat16))
+        conv5, conv4, saved, _ = self._trunk_forward(data, at_conv4=fork, im_info=im_info)
         # (a float32 trunk -- cfg.trunk_fp32, parity tests -- hands bf16 copies to the bf16 heads and takes their gradients back as float32)
         conv5, conv4 = conv5.to(torch.bfloat16), conv4.to(torch.bfloat16)
         feat = self._conv(conv5, 'conv_new_1', relu=True, bias=self.b('conv_new_1'))
-        if late_relayout:
-            self._relayout.run()
-            if br.get('bwd') is not None:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    rpn_backward(*br.pop('bwd'))
-        if side is not None:
-            if rpn_bwd_side:
-                main.wait_event(br['ev'])
-            else:
-                main.wait_stream(side)
-            # the branch's tensors were allocated on the side stream and are consumed on the main one through the backward pass:
-            # tell the caching allocator, so that their blocks are not handed out again on the side stream while main still reads them
-            if not torch.cuda.is_current_stream_capturing():      # (a capture's private pool keeps its blocks for the graph's lifetime)
-                for v in br.values():
-                    if torch.is_tensor(v) and v.is_cuda:
-                        v.record_stream(main)
-        r, d_rpn, rois_t, label, bbox_target, bbox_weight, N, R = (br[k] for k in ('r', 'd_rpn', 'rois_t', 'label', 'bbox_target',
-                                                                                      'bbox_weight', 'N', 'R'))
+        # W^T / tap-flipped copies of the current weights for every data-gradient product: only the BACKWARD reads them, so they are made
+        # here, where the main stream otherwise waits for the proposals (one image: the RPN branch's single-workgroup sort / NMS kernels
+        # are the longer path and leave the chip idle)
+        self._relayout.run()
+        if rpn_bwd_side:
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                rpn_backward(*br.pop('bwd'))
+            main.wait_event(br['ev'])
+        else:
+            main.wait_stream(side)
+        # the branch's tensors were allocated on the side stream and are consumed on the main one through the backward pass:
+        # tell the caching allocator, so that their blocks are not handed out again on the side stream while main still reads them
+        if not torch.cuda.is_current_stream_capturing():      # (a capture's private pool keeps its blocks for the graph's lifetime)
+            for v in br.values():
+                if torch.is_tensor(v) and v.is_cuda:
+                    v.record_stream(main)
+        rois_t, label, bbox_target, bbox_weight, N, R = (br[k] for k in ('rois_t', 'label', 'bbox_target', 'bbox_weight', 'N', 'R'))
         r5 = rois_t.view(B * R, 5)
         if c.dcn:
             sc_ = 1.0 / c.feat_stride
@@ -640,12 +546,8 @@ class Trainer(object):
             d_feat = d_feat.permute(0, 2, 3, 1).to(bt)          # NHWC memory already: one conversion pass
         g = T.relu_bwd(d_feat, feat)
         d_x, dw = T.conv1x1_bwd(conv5, self.w('conv_new_1'), g, w_t=self.wt('conv_new_1'), keep_splits=True, wgrad_to=self._wg('conv_new_1'))
-        T.colsum_add(g, self._bg('conv_new_1'))
-        # RPN head backward (joins the trunk at conv4)
-        if rpn_bwd_side:
-            main.wait_stream(side)
-        else:
-            rpn_backward(conv4, r, d_rpn)
+        T.colsum_add(g, *self._bg('conv_new_1'))
+        main.wait_stream(side)          # the RPN head's backward (joins the trunk at conv4)
         d_conv4_rpn = br['d_conv4_rpn']
         if self.trunk_fp32:
             d_x, d_conv4_rpn = d_x.float(), d_conv4_rpn.float()
@@ -670,7 +572,6 @@ class Trainer(object):
             self._bucket_ready('heads')
         prev_bucket = None
         masked = False            # d_x already carries the ReLU mask of the unit's output (relnet_gemm_nt_mask of the unit after it)
-        since_flush = 0
         order = list(reversed(saved))
         for pos, (stage, nm, stride, dil, proj, x_in, y1, y2, o, off) in enumerate(order):
             bucket = self._unit_bucket[nm]
@@ -679,7 +580,6 @@ class Trainer(object):
                     self._bucket_ready('res5', 'heads')        # both complete at this point: one cut, two collectives
                 else:
                     self._bucket_ready(prev_bucket)
-                since_flush = 0
             prev_bucket = bucket
             n1, na, nb, nc_ = 'res%s_branch1' % nm, 'res%s_branch2a' % nm, 'res%s_branch2b' % nm, 'res%s_branch2c' % nm
             if inject.get(nm) is not None:       # a second consumer of this unit's output (RPN head at conv4, FPN laterals)
@@ -713,11 +613,10 @@ class Trainer(object):
                 # resolution for a stride-2 unit, then scattered to the input's resolution once, with the previous unit's ReLU mask in the same
                 # pass when that output has no other consumer (was: 2 zero fills + 2 strided copies + a full-resolution add + relu_bwd)
                 prev_nm = order[pos + 1][1] if pos + 1 < len(order) else None
-                fold_on = os.environ.get('RELNET_TRAIN_FOLD', '1') != '0'          # (A/B switch: 0 = the separate passes)
-                lr = stride != 1 and fold_on
+                lr = stride != 1
                 # a second consumer's gradient of this unit's INPUT (the RPN head at conv4, in front of the stride-1 res5a) rides in the first
                 # GEMM's epilogue; the input's ReLU mask can then ride in the second one's
-                inj = inject.get(prev_nm) if (fold_on and stride == 1 and not first and prev_nm is not None) else None
+                inj = inject.get(prev_nm) if (stride == 1 and not first and prev_nm is not None) else None
                 fold = inj is not None and inj.dtype == g_y1.dtype and tuple(inj.shape) == tuple(x_in.shape) and inj.is_contiguous()
                 d_a, dw = T.conv1x1_bwd(x_in, self.w(na), g_y1, stride=stride, need_dx=not first, w_t=self.wt(na), keep_splits=True, wgrad_to=self._wg(na, self.bn_scale[na]),
                                         dx_add=inj if fold else None, low_res=lr)
@@ -725,10 +624,10 @@ class Trainer(object):
                     inject = {k: v for k, v in inject.items() if k != prev_nm}
                 can_mask = self.mask_epilogue and not first and prev_nm is not None and inject.get(prev_nm) is None
                 d_s, dw = T.conv1x1_bwd(x_in, self.w(n1), g_out, stride=stride, need_dx=not first, w_t=self.wt(n1),
-                                        dx_add=d_a if (not first and (lr or stride == 1)) else None, keep_splits=True, wgrad_to=self._wg(n1, self.bn_scale[n1]), low_res=lr,
-                                        out_mask=x_in if (can_mask and fold_on and stride == 1) else None)
-                d_x = None if first else (d_s if (lr or stride == 1) else d_s + d_a)
-                masked = can_mask and fold_on and stride == 1
+                                        dx_add=None if first else d_a, keep_splits=True, wgrad_to=self._wg(n1, self.bn_scale[n1]), low_res=lr,
+                                        out_mask=x_in if (can_mask and stride == 1) else None)
+                d_x = None if first else d_s
+                masked = can_mask and stride == 1
                 if lr and not first:
                     d_x = T.strided_scatter(d_s, tuple(x_in.shape), stride, mask=x_in if can_mask else None)
                     masked = can_mask
@@ -740,10 +639,6 @@ class Trainer(object):
                 d_x, dw = T.conv1x1_bwd(x_in, self.w(na), g_y1, dx_add=g_out, w_t=self.wt(na), keep_splits=True, wgrad_to=self._wg(na, self.bn_scale[na]),
                                         out_mask=x_in if can_mask else None)
                 masked = can_mask
-            since_flush += 1
-            if self._wgrad_side is not None and since_flush >= self.wgrad_overlap:
-                self._flush_wgrads(final=False)       # this group of weight gradients starts now, beside the next units' data gradients
-                since_flush = 0
         self._bucket_ready(prev_bucket)
 
     def _head_forward_backward(self, pooled2, rois_t, N, label, bbox_target, bbox_weight, im_info, gt_boxes, num_gt, out,
@@ -823,12 +718,12 @@ class Trainer(object):
         cls_score [B,N,81] fp32, bbox_pred [B,N,8] (BlockGrad), rois [B,N,5], feat = fc_all_2_relu[:, :N] bf16.
         Returns (d cls_score [B,N,81] fp32, d feat [B,N,1024] (bf16, as the projection's backward GEMM leaves it), losses); with d_cls_out [B,R,81] fp32 (contiguous, R >= N) the
         class-score gradient is accumulated into d_cls_out[:, :N] instead and None is returned in its place.
-        cfg.lnms_fused_glue (default on; RELNET_LNMS_GLUE=0 = the tensor-operator chains of rounds 3 - 5, kept for the equality test):
+        cfg.lnms_fused_glue (default on; off = the tensor-operator chains of rounds 3 - 5, kept for the equality test):
         the element-wise chains of the branch run as single kernels (csrc/lnms_train.hip)."""
         import ctypes
         from . import lib as _lib
         c = self.cfg
-        fused = bool(getattr(c, 'lnms_fused_glue', os.environ.get('RELNET_LNMS_GLUE', '1') != '0'))
+        fused = bool(getattr(c, 'lnms_fused_glue', True))
         B, N, C1 = cls_score.shape
         C, F, Tn = C1 - 1, c.first_n, len(c.nms_target_thresh)
         dev, bt, s_ = cls_score.device, torch.bfloat16, ops._stream()
@@ -872,7 +767,7 @@ class Trainer(object):
         mod.bp = self.b('nms_pair_pos_fc1_1')
         wp_t, bp = pack_pair_pos([mod], dev)
         cb = class_boxes.view(BC, F, 4)
-        if fused and n_valid is None and getattr(c, 'lnms_geometry_table', os.environ.get('RELNET_LNMS_GEOM_TABLE', '1') != '0'):
+        if fused and n_valid is None:
             # ln G once per IMAGE (B N^2 pairs instead of B C F^2: 9 x fewer at 300 rois / 80 classes / first_n 100), then gathered per class by its ranks
             # (relnet_lnms_gather_bias): the class's boxes are the image's boxes re-ordered, same arithmetic on the same pairs -> bit-identical
             img = ops.geometry_bias(boxes, wp_t, bp, N, fast32=True)[0]                    # [B,16,N,Npad]
@@ -920,44 +815,36 @@ class Trainer(object):
             # (Tn real of 64 padded output columns), the bias gradient in its grouped column sum (was 8 library launches: transpose, fills, casts, sums)
             d_allf = ops.gemm_nt(d_logit_p, wl_t)
             T._wg_call(self._wg('nms_logit'), d_logit_p, allf.view(BC * F, 128), cout=Tn)
-            T.colsum_add(d_logit_p[:, :Tn], self._bg('nms_logit'))
+            T.colsum_add(d_logit_p[:, :Tn], *self._bg('nms_logit'))
         else:
             d_allf, dw, db = T.linear_bwd(allf.view(BC * F, 128), w_logit, d_logit_p, w_t=None, keep_splits=True)
             self._add_wgrad('nms_logit', dw.sum(0)[:Tn]); self._add_bgrad('nms_logit', db[:Tn])
         g = T.relu_bwd(d_allf, allf.view(BC * F, 128))                                          # [BC*F,128] bf16
         dY = self._scratch('nms_dy_pad', (BC, F, 1024), bt)                   # persistent: columns 8 .. 63 of every head stay zero
         dY.view(BC, F, 16, 64)[..., :8] = g.view(BC, F, 16, 8)
+        # gradients through relation.GradSink: [dQ | dK | dVW] packed once, ONE projection-backward GEMM (K = 3072) with the residual
+        # gradient g in its epilogue; the [Wq; Wk] product goes straight into the flat buffer, the padded Wout product through a
+        # [1024, 128] scratch whose 8 real rows per head are then added to the compact [128, 128] gradient
         wcat_t = self._relayout.get('rel_cat_nms')
-        if wcat_t is not None and getattr(c, 'relation_sink', os.environ.get('RELNET_REL_SINK', '1') != '0'):
-            # gradients through relation.GradSink: [dQ | dK | dVW] packed once, ONE projection-backward GEMM (K = 3072) with the residual
-            # gradient g in its epilogue; the [Wq; Wk] product goes straight into the flat buffer, the padded Wout product through a
-            # [1024, 128] scratch whose 8 real rows per head are then added to the compact [128, 128] gradient
-            gq = self.W.view(self.W.grad, 'nms_qk_1')
-            glo = self._scratch('nms_dwout_pad', (1024, 128), torch.float32)
-            glo.zero_()
+        assert wcat_t is not None
+        gq = self.W.view(self.W.grad, 'nms_qk_1')
+        glo = self._scratch('nms_dwout_pad', (1024, 128), torch.float32)
+        glo.zero_()
 
-            def wg(dy2d, x2d):
-                ops.wgrad_tn(dy2d[:, :2048], x2d, out=gq.view(2048, 128))
-                ops.wgrad_tn(dy2d[:, 2048:], x2d, out=glo)
-            sink = GradSink(wcat_t, g.view(BC, F, 128), wg, self._bg('nms_qk_1'), None,
-                            self.W.view(self.W.grad, 'nms_pair_pos_fc1_1'), self._bg('nms_pair_pos_fc1_1'), self._scratch, defer=self._defer)
-            r = attention_module_backward(xr, cb, None, dY, nongt_dim=F, index=1, dtype=bt, packed=mod, cache=lcache, sink=sink)
-            self.W.view(self.W.grad, 'nms_linear_out_1').view(16, 8, 128).add_(glo.view(16, 64, 128)[:, :8])
-            T.colsum_add(g.view(BC * F, 128), self._bg('nms_linear_out_1'))    # (dY's real columns are g's columns)
-            d_x = r['d_roi_feat'].view(B, C, F, 128)                            # bf16: residual + module
-        else:
-            r = attention_module_backward(xr, cb, None, dY, nongt_dim=F, index=1, dtype=bt, packed=mod, cache=lcache)
-            self._add_wgrad('nms_qk_1', torch.cat([r['query_1_weight'], r['key_1_weight']], 0))
-            self._add_bgrad('nms_qk_1', torch.cat([r['query_1_bias'], r['key_1_bias']], 0))
-            self._add_wgrad('nms_linear_out_1', r['linear_out_1_weight'].reshape(16, 64, 128)[:, :8].reshape(128, 128))
-            self._add_bgrad('nms_linear_out_1', r['linear_out_1_bias'].view(16, 64)[:, :8].reshape(128))
-            self._add_wgrad('nms_pair_pos_fc1_1', r['pair_pos_fc1_1_weight']); self._add_bgrad('nms_pair_pos_fc1_1', r['pair_pos_fc1_1_bias'])
-            d_x = (r['d_roi_feat'] + g.view(BC, F, 128).float()).view(B, C, F, 128)             # residual + module
+        def wg(dy2d, x2d):
+            ops.wgrad_tn(dy2d[:, :2048], x2d, out=gq.view(2048, 128))
+            ops.wgrad_tn(dy2d[:, 2048:], x2d, out=glo)
+        sink = GradSink(wcat_t, g.view(BC, F, 128), wg, self._bg('nms_qk_1'), None,
+                        self.W.view(self.W.grad, 'nms_pair_pos_fc1_1'), self.Bv.view(self.Bv.grad, 'nms_pair_pos_fc1_1'), self._scratch)
+        r = attention_module_backward(xr, cb, None, dY, nongt_dim=F, index=1, dtype=bt, packed=mod, cache=lcache, sink=sink)
+        self.W.view(self.W.grad, 'nms_linear_out_1').view(16, 8, 128).add_(glo.view(16, 64, 128)[:, :8])
+        T.colsum_add(g.view(BC * F, 128), *self._bg('nms_linear_out_1'))    # (dY's real columns are g's columns)
+        d_x = r['d_roi_feat'].view(B, C, F, 128)                            # bf16: residual + module
         if fused and d_x.is_contiguous():
             d_rank = torch.zeros((F, 128), device=dev, dtype=torch.float32)                     # sum over (image, class): one column-sum launch (fp32 accumulation)
             _lib.call('relnet_colsum_add', d_x.data_ptr(), F * 128, BC, F * 128, ops._dt(d_x), d_rank.data_ptr(), s_)
             T._wg_call(self._wg('nms_rank'), d_rank.to(bt), self.rank_emb)
-            T.colsum_add(d_rank, self._bg('nms_rank'))
+            T.colsum_add(d_rank, *self._bg('nms_rank'))
         else:
             d_rank = d_x.sum((0, 1), dtype=torch.float32)                                       # [F,128] (fp32 accumulation whatever d_x's dtype)
             self._add_wgrad('nms_rank', T.wgrad(d_rank.to(bt), self.rank_emb)); self._add_bgrad('nms_rank', d_rank.sum(0))
@@ -1007,27 +894,17 @@ class Trainer(object):
         gradients straight into the flat buffers (relation.GradSink: one pack kernel, one projection-backward GEMM with the residual
         gradient in its epilogue, one queued weight-gradient product for [Wq; Wk; Wout], column-sum kernels for the biases)."""
         g = T.relu_bwd(d_x.contiguous(), x_act)
-        d = mod.wqk.shape[0] // 2
         oq, sq = self.W.slices['qk_%d' % i]
         oo, so = self.W.slices['linear_out_%d' % i]
         wcat_t = self._relayout.get('rel_cat_%d' % i)
-        if wcat_t is not None and oo == oq + sq[0] * sq[1] and getattr(self.cfg, 'relation_sink', os.environ.get('RELNET_REL_SINK', '1') != '0'):
-            g3 = self.W.grad[oq:oq + (sq[0] + so[0]) * sq[1]].view(sq[0] + so[0], sq[1])      # d[Wq; Wk; Wout], adjacent slices of the flat buffer
-            sink = GradSink(wcat_t, g, lambda dy2d, x2d: T._wg_call((g3, None, self._wq), dy2d, x2d),
-                            self._bg('qk_%d' % i), self._bg('linear_out_%d' % i),
-                            self.W.view(self.W.grad, 'pair_pos_fc1_%d' % i), self._bg('pair_pos_fc1_%d' % i), self._scratch, defer=self._defer)
-            r = attention_module_backward(f, rois, None, g, nongt_dim=N, index=i, dtype=torch.bfloat16, packed=mod, key_count=key_count,
-                                          cache=cache, sink=sink)
-            return r['d_roi_feat']
+        assert wcat_t is not None and oo == oq + sq[0] * sq[1]          # (linear_out_i is registered right after qk_i)
+        g3 = self.W.grad[oq:oq + (sq[0] + so[0]) * sq[1]].view(sq[0] + so[0], sq[1])      # d[Wq; Wk; Wout], adjacent slices of the flat buffer
+        sink = GradSink(wcat_t, g, lambda dy2d, x2d: T._wg_call((g3, None, self._wq), dy2d, x2d),
+                        self._bg('qk_%d' % i), self._bg('linear_out_%d' % i),
+                        self.W.view(self.W.grad, 'pair_pos_fc1_%d' % i), self.Bv.view(self.Bv.grad, 'pair_pos_fc1_%d' % i), self._scratch)
         r = attention_module_backward(f, rois, None, g, nongt_dim=N, index=i, dtype=torch.bfloat16, packed=mod, key_count=key_count,
-                                      cache=cache)
-        self._add_wgrad('qk_%d' % i, torch.cat([r['query_%d_weight' % i], r['key_%d_weight' % i]], 0))
-        self._add_bgrad('qk_%d' % i, torch.cat([r['query_%d_bias' % i], r['key_%d_bias' % i]], 0))
-        self._add_wgrad('linear_out_%d' % i, r['linear_out_%d_weight' % i].reshape(d, -1))
-        self._add_bgrad('linear_out_%d' % i, r['linear_out_%d_bias' % i])
-        self._add_wgrad('pair_pos_fc1_%d' % i, r['pair_pos_fc1_%d_weight' % i])
-        self._add_bgrad('pair_pos_fc1_%d' % i, r['pair_pos_fc1_%d_bias' % i])
-        return (r['d_roi_feat'] + g.float()).to(torch.bfloat16)          # residual path + module path
+                                      cache=cache, sink=sink)
+        return r['d_roi_feat']
 
     # ---- checkpoint view -----------------------------------------------------------------------------------
     def export_params(self):
@@ -1115,10 +992,6 @@ class Trainer(object):
             half = res4[len(res4) // 2]                                        # '4b11' of 4a, 4b1 .. 4b22
             cuts = [0, first('res4'), first('res' + half + '_'), first('res5'), trunk_end, self.W.size]
             self._bucket_names = ('res3', 'res4_lo', 'res4_hi', 'res5', 'heads')
-            if getattr(self.cfg, 'split_res4_bucket', True) is False:
-                cuts = [0, first('res4'), first('res5'), trunk_end, self.W.size]
-                self._bucket_names = ('res3', 'res4_lo', 'res5', 'heads')
-                half = None
             assert cuts == sorted(set(cuts)), cuts
             self._bucket_cuts = cuts
             self._unit_bucket = {}
@@ -1136,7 +1009,7 @@ class Trainer(object):
 
     def _bucket_ready(self, *names):
         """Called by the backward pass when the last gradient of a bucket (or of several at once) has been queued (no-op on one rank)."""
-        self._flush_wgrads()         # the bucket is complete only once its queued weight gradients have been launched (and joined)
+        self._flush_wgrads()         # the bucket is complete only once its queued gradient work has been launched
         bk = self._grad_buckets()
         idxs = [self._bucket_names.index(n) for n in names]
         cut = getattr(self, '_capture_cut', None)
@@ -1425,7 +1298,7 @@ class FPNTrainer(Trainer):
         for lvl in (4, 8, 16, 32):
             n3, n1 = 'fpn_ft%d_3x3' % lvl, 'fpn_ft%d_1x1' % lvl
             d_top, dw = T.conv3x3_bwd(tops[lvl], self._dgrad_w(n3, 256), d_feats[lvl], dil=1, keep_splits=True, wgrad_to=self._wg(n3))
-            T.colsum_add(d_feats[lvl], self._bg(n3))             # (bias gradients: the bucket's grouped column-sum launch)
+            T.colsum_add(d_feats[lvl], *self._bg(n3))             # (bias gradients: the bucket's grouped column-sum launch)
             if lvl in d_tops:                                    # + the gradient that came down from the finer level (fp32 block sums)
                 d_top = torch.add(d_top, d_tops[lvl]).to(bt)
             if lvl < 32:       # tops[lvl] = lateral + up2x(tops[2 lvl]): adjoint of nearest upsampling = 2x2 block sums (fp32 accumulation, read as bf16)
@@ -1433,7 +1306,7 @@ class FPNTrainer(Trainer):
                 d_tops[lvl * 2] = d_top.view(Bh, Hh // 2, 2, Wh // 2, 2, Ch).sum((2, 4), dtype=torch.float32)
             d_top = d_top.contiguous()
             d_src, dw = T.conv1x1_bwd(src[lvl], self.w(n1), d_top, need_dx=(lvl != 4), w_t=self.wt(n1), keep_splits=True, wgrad_to=self._wg(n1))   # res2c is frozen
-            T.colsum_add(d_top, self._bg(n1))
+            T.colsum_add(d_top, *self._bg(n1))
             if lvl == 32:
                 d_c5 = d_src
             elif lvl == 16:

@@ -43,7 +43,8 @@ def strided_scatter(low, shape, stride, mask=None):
 
 class ColsumQueue(object):
     """Bias-gradient column sums collected for ONE grouped launch per gradient bucket (relnet_colsum_add_grouped, <= 16 problems per
-    launch).  `add` keeps the operand alive until `flush`; operands the grouped kernel does not take (fp32, ragged widths) are summed at once."""
+    launch).  `add` keeps the operand alive until `flush`; operands the grouped kernel does not take (fp32, ragged widths) are summed at once.
+    The operand must not be modified in place before the flush: `flush` checks its version counter before anything is launched."""
 
     def __init__(self):
         self.items = []
@@ -56,38 +57,34 @@ class ColsumQueue(object):
         if not ok:
             _lib.call('relnet_colsum_add', x2.data_ptr(), x2.stride(0), x2.shape[0], x2.shape[1], _dt(x2), out.data_ptr(), _stream())
             return
-        self.items.append((x2, out))
+        self.items.append((x2, out, x2._version))
 
     def flush(self):
         import ctypes as C
         items, self.items = self.items, []
+        for x, _, v in items:
+            assert x._version == v, "a queued bias-gradient operand %s was modified in place before the flush" % (tuple(x.shape),)
         for i in range(0, len(items), 16):
             grp = items[i:i + 16]
             n = len(grp)
-            xs = (C.c_void_p * n)(*[x.data_ptr() for x, _ in grp])
-            lds = (C.c_long * n)(*[x.stride(0) for x, _ in grp])
-            rows = (C.c_long * n)(*[x.shape[0] for x, _ in grp])
-            cols = (C.c_int * n)(*[x.shape[1] for x, _ in grp])
-            outs = (C.c_void_p * n)(*[o.data_ptr() for _, o in grp])
+            xs = (C.c_void_p * n)(*[x.data_ptr() for x, _, _ in grp])
+            lds = (C.c_long * n)(*[x.stride(0) for x, _, _ in grp])
+            rows = (C.c_long * n)(*[x.shape[0] for x, _, _ in grp])
+            cols = (C.c_int * n)(*[x.shape[1] for x, _, _ in grp])
+            outs = (C.c_void_p * n)(*[o.data_ptr() for _, o, _ in grp])
             _lib.call('relnet_colsum_add_grouped', xs, lds, rows, cols, outs, n, _stream())
         return items            # (still referenced by the caller until the launch has been issued)
 
 
-#: the queue bias-gradient sums go to while a training step is being recorded (train.Trainer sets it around forward_backward and flushes it
-#: when a gradient bucket completes); None = every colsum_add launches at once
-COLSUM_QUEUE = None
-
-
-def colsum_add(x, out):
+def colsum_add(x, out, queue=None):
     """out[c] += sum over all leading dims of x[..., c]  (bias gradient accumulated in place; x bf16 / fp32 with a dense last dim,
-    out fp32 [C] -- a view of the flat gradient buffer).  With an active COLSUM_QUEUE the sum is deferred to the queue's grouped launch:
-    x must not be modified before that flush."""
+    out fp32 [C] -- a view of the flat gradient buffer).  queue (ColsumQueue): the sum is deferred to the queue's grouped launch."""
     C = x.shape[-1]
     assert out.dtype == torch.float32 and out.numel() == C and out.is_contiguous() and x.stride(-1) == 1
     x2 = x.reshape(-1, C)
     _chk(x2, out)
-    if COLSUM_QUEUE is not None:
-        COLSUM_QUEUE.add(x2, out)
+    if queue is not None:
+        queue.add(x2, out)
         return
     _lib.call('relnet_colsum_add', x2.data_ptr(), x2.stride(0), x2.shape[0], C, _dt(x2), out.data_ptr(), _stream())
 
@@ -158,8 +155,9 @@ def _tn_ok(dy2d, x):
 
 def linear_bwd(x2d, w, dy2d, need_dx=True, w_t=None, keep_splits=False, wgrad_to=None, relu_mask=None, bgrad_to=None):
     """y = x W^T + b  ->  (dx [P,K] in x's dtype | None, dW [N,K] fp32, db [N] fp32).
-    wgrad_to = (grad [N,K] fp32 view, row_scale | None): the weight gradient is ACCUMULATED there by relnet_wgrad (one
+    wgrad_to = (grad [N,K] fp32 view, row_scale | None[, ops.WgradQueue]): the weight gradient is ACCUMULATED there by relnet_wgrad (one
     kernel straight from the row-major operands) and None is returned in its place.
+    bgrad_to = (grad [N] fp32 view, ColsumQueue | None): likewise for the bias gradient (colsum_add).
     relu_mask [P,K] (x's dtype): dx is zeroed where relu_mask <= 0 inside the GEMM epilogue (x = relu(.) fused in the forward)."""
     dx = None
     gran = 64 if dy2d.dtype == torch.bfloat16 else 16
@@ -173,7 +171,7 @@ def linear_bwd(x2d, w, dy2d, need_dx=True, w_t=None, keep_splits=False, wgrad_to
         dx = ops.gemm_nt(dyp, w_t) if relu_mask is None else ops.gemm_nt(dyp, w_t, resid=relu_mask, relu=2)
     db = None
     if bgrad_to is not None:            # bias gradient accumulated straight into its slice of the flat buffer (one kernel)
-        colsum_add(dy2d, bgrad_to)
+        colsum_add(dy2d, *bgrad_to)
     else:
         db = dy2d.float().sum(0)
     if wgrad_to is not None and _tn_ok(dyp, x2d):

@@ -303,7 +303,7 @@ def test_colsum_add_accumulates_bias_gradients(shape, dt):
         assert (out2.double() - xs.double().sum(0)).abs().max().item() <= 2e-6 * scale + 1e-5
 
 
-def test_colsum_queue_one_grouped_launch_for_a_bucket():
+def test_colsum_queue_given_explicitly_one_grouped_launch_for_a_bucket():
     """train_ops.ColsumQueue / relnet_colsum_add_grouped (round 6): the 12 - 13 bias gradients of a training step in one launch per <= 16
     problems.  Mixed shapes (19 152 pixels x 128 / 256 channels, 2 464 rois x 1 024 / 2 048, a row-strided slice, a 100-row matrix), 20 problems
     (two launches), accumulation on top of existing values; an fp32 and a ragged-width operand take the single-launch kernel at once."""
@@ -316,22 +316,48 @@ def test_colsum_queue_one_grouped_launch_for_a_bucket():
     odd = [torch.randn(2464, 89, generator=g).cuda(), torch.randn(50, 12, generator=g).to(bf).cuda()]
     outs = [torch.full((x.shape[1],), 0.25, device='cuda') for x in xs + odd]
     q = T.ColsumQueue()
-    T.COLSUM_QUEUE = q
-    try:
-        for x, o in zip(xs + odd, outs):
-            T.colsum_add(x, o)
-        assert len(q) == len(xs)                    # the two odd operands were summed immediately
-        for x, o in zip(odd, outs[len(xs):]):
-            assert (o.double() - (x.double().sum(0) + 0.25)).abs().max().item() <= 1e-4 * max(x.double().abs().sum(0).max().item(), 1)
-        assert torch.equal(outs[0], torch.full_like(outs[0], 0.25))              # (queued: nothing launched yet)
-        q.flush()
-        assert len(q) == 0
-    finally:
-        T.COLSUM_QUEUE = None
+    for x, o in zip(xs + odd, outs):
+        T.colsum_add(x, o, q)
+    assert len(q) == len(xs)                    # the two odd operands were summed immediately
+    for x, o in zip(odd, outs[len(xs):]):
+        assert (o.double() - (x.double().sum(0) + 0.25)).abs().max().item() <= 1e-4 * max(x.double().abs().sum(0).max().item(), 1)
+    assert torch.equal(outs[0], torch.full_like(outs[0], 0.25))              # (queued: nothing launched yet)
+    q.flush()
+    assert len(q) == 0
     for x, o in zip(xs, outs):
         want = x.double().sum(0) + 0.25
         scale = x.double().abs().sum(0).max().item()
         assert (o.double() - want).abs().max().item() <= 2e-6 * scale + 1e-5, tuple(x.shape)
+
+
+def test_gradient_queues_refuse_an_operand_modified_before_the_flush():
+    """ColsumQueue and WgradQueue launch after the operands were queued: an operand written in place in between (its version counter moved)
+    makes the flush raise before anything is launched.  Writing the gradient buffer that `out` is a view of is allowed."""
+    ops, T = _mods()
+    g = torch.Generator().manual_seed(6)
+    bf = torch.bfloat16
+    x = torch.randn(256, 64, generator=g).to(bf).cuda()
+    dy = torch.randn(256, 128, generator=g).to(bf).cuda()
+    grad = torch.zeros(128 * 64 + 64, device='cuda')
+    wout, bout = grad[:128 * 64].view(128, 64), grad[128 * 64:]
+    cq, wq = T.ColsumQueue(), ops.WgradQueue()
+    T.colsum_add(x, bout, cq)
+    wq.add(dy, x, wout)
+    x[0, 0] = 1.0
+    with pytest.raises(AssertionError, match='modified in place'):
+        cq.flush()
+    with pytest.raises(AssertionError, match='modified in place'):
+        wq.flush()
+    torch.cuda.synchronize()
+    assert not grad.any()                        # nothing was launched
+    assert len(cq) == 0 and len(wq) == 0         # (and nothing is left to launch later)
+    T.colsum_add(x, bout, cq)                    # unchanged operands: the flushes go through
+    wq.add(dy, x, wout)
+    grad.add_(0.0)                               # (the buffer the outputs are views of is no operand)
+    cq.flush(); wq.flush()
+    torch.cuda.synchronize()
+    assert torch.allclose(bout, x.float().sum(0), rtol=1e-3, atol=1e-3)
+    assert torch.allclose(wout, dy.float().t() @ x.float(), rtol=1e-2, atol=1e-2)
 
 
 @pytest.mark.parametrize('tile', [0, 1, 3, 4, 5, 22])

@@ -165,13 +165,24 @@ def test_training_step_gradients_match_autograd(learn_nms, dcn, chain, monkeypat
     assert len(want) == len(tr.W.slices)
 
 
-def test_training_steps_reduce_the_loss_and_update_only_trainable():
+def test_training_steps_reduce_the_loss_and_leave_the_frozen_backbone_unchanged():
     H, W, G = 128, 160, 4
     p, cfg, data, gt, L, Tg, Wg, train = _setup(H, W, G, 33)
     tr = train.Trainer(p, cfg, im_hw=(H, W))
     d = lambda a: torch.as_tensor(a).cuda()
     batch = (data.cuda(), torch.tensor([[H, W, 1.0]]).cuda(), d(gt), d(L[None]), d(Tg[None]), d(Wg[None]))
-    frozen_before = {k: v.clone() for k, v in tr.frozen.items()}
+    fb = tr._frozen_backbone                                       # conv1 + res2 as the step runs them: packed weights and biases
+
+    def frozen():
+        ts = {'w_stem': fb.w_stem}
+        for n, (w, b, _) in fb.wp.items():
+            ts[n + ':w'], ts[n + ':b'] = w, b
+        ts.update({n + ':b32': b for n, b in fb.b32.items()})
+        for n, parts in list(fb.chain.items()) + list(fb.chain_proj.items()) + list(fb.halo3.items()):
+            ts.update({'%s:%d' % (n, i): t for i, t in enumerate(parts) if torch.is_tensor(t)})
+        return ts
+    frozen_before = {k: v.clone() for k, v in frozen().items()}
+    assert 'res2a_branch2b:w' in frozen_before and 'conv1:b32' in frozen_before
     w0 = tr.W.master.clone()
     first = None
     for it in range(6):
@@ -180,7 +191,8 @@ def test_training_steps_reduce_the_loss_and_update_only_trainable():
         first = v if first is None else first
     assert v < first                                               # SGD on a fixed batch reduces the RPN box loss
     assert torch.isfinite(tr.W.master).all() and not torch.equal(tr.W.master, w0)
-    assert all(torch.equal(tr.frozen[k], frozen_before[k]) for k in frozen_before)
+    frozen_after = frozen()
+    assert frozen_after.keys() == frozen_before.keys() and all(torch.equal(frozen_after[k], frozen_before[k]) for k in frozen_before)
     assert torch.equal(tr.W.work, tr.W.master.to(torch.bfloat16))  # bf16 working copy refreshed by the optimizer kernel
     # gradient buckets (dist.BucketedAllReduce): announced by the backward pass heads -> res5 -> res4 (units b11 .. b22) -> res4 (a .. b10)
     # -> res3, and the five contiguous ranges hold exactly those parameters
@@ -496,25 +508,23 @@ def test_captured_step_in_bucket_segments_equals_eager():
         assert torch.isfinite(tr.W.master).all()
 
 
-def test_round5_trunk_backward_forms_agree():
+def test_trunk_backward_mask_epilogue_on_and_off_agree():
     """Backward of the trunk from the SAME saved activations (forward on the chain kernels, thresholds lowered for this small map)
-    in its two forms: round 5 (ReLU mask of a unit's output gradient in the data-gradient GEMM's epilogue -- relnet_gemm_nt_mask --,
-    weight gradients on a side stream every few units) against round 4 (GEMM + relnet_relu_bwd, one grouped weight-gradient launch
-    per bucket on the main stream).  No forward difference, no discrete decision: the gradients agree up to the order of the
+    with the ReLU mask of a unit's output gradient in the data-gradient GEMM's epilogue (relnet_gemm_nt_mask) against
+    GEMM + relnet_relu_bwd.  No forward difference, no discrete decision: the gradients agree up to the order of the
     fp32 atomic adds (cosine >= 0.99999, norm within 0.1 %).  The chain forward itself is checked against float64 autograd by
     test_training_step_gradients_match_autograd[chain] and unit by unit by test_gpu_bottleneck.py."""
     import relnet_amd  # noqa: F401
     from relnet_amd import ops
     H, W, G = 256, 320, 4
     p, cfg, data, gt, L, Tg, Wg, train = _setup(H, W, G, 52)
-    cfg.wgrad_overlap = 3
     data2 = torch.cat([data, data.flip(3)]).cuda()
     old_min = dict(ops.CHAIN_MIN_PIXELS)
     try:
         for k in ops.CHAIN_MIN_PIXELS:
             ops.CHAIN_MIN_PIXELS[k] = 1                       # run the chain kernels on this small map (res4: 2 x 16 x 20 pixels)
         tr = train.Trainer(p, cfg, im_hw=(H, W))
-        assert tr.chain_units and tr.mask_epilogue and tr._wgrad_side is not None
+        assert tr.chain_units and tr.mask_epilogue
         tr._relayout.run(); tr._fragpack.run()
         conv5, conv4, saved, _ = tr._trunk_forward(data2)
     finally:
@@ -530,9 +540,9 @@ def test_round5_trunk_backward_forms_agree():
         return tr.W.grad.clone()
 
     g_new = backward()
-    side, tr.mask_epilogue, tr._wgrad_side = tr._wgrad_side, False, None
+    tr.mask_epilogue = False
     g_old = backward()
-    tr.mask_epilogue, tr._wgrad_side = True, side
+    tr.mask_epilogue = True
     assert torch.isfinite(g_new).all() and float(g_old.norm()) > 0
     bad = []
     for name in tr.W.slices:
