@@ -682,6 +682,31 @@ int relnet_roi_pool_fpn_bwd_ex(const void* grad_out, const int* argmax, const lo
 int relnet_wgrad_accumulate(const float* parts, int splits, long rows, int cols, const float* row_scale, float* grad,
                             void* stream);
 
+/* ---- COCO bbox evaluation (csrc/cocoeval.hip), bit-identical to dataset/cocoeval.py -------------------------------------
+ * relnet_coco_match = evaluateImg (lib/dataset/pycocotools/cocoeval.py:189-273) for every (area range, IoU threshold) pair of one
+ * batch of images in one launch.  det [B, S_in, 6] float32 (det_dtype 0) or float64 (1): class, score, box; box_xywh 0 = (x1, y1,
+ * x2, y2) scored as results_list does (w = x2 - x1 + 1; round_f32: float64 rows rounded to float32 first, as pred_eval's .float()),
+ * 1 = (x, y, w, h).  class_to_cat [n_classes]: category position or -1.  Ground truth: CSR gt_off [n_images * K + 1] over (image,
+ * category), annotation order inside a cell; gt_box [n_gt, 4] (x, y, w, h) float64; gt_flags bit 0 iscrowd, bit 1 + a ignored in
+ * area range a (ignore | iscrowd | area outside the inclusive range).  iou_thr [T], area_rng [A, 2] float64.  gtm_scratch
+ * [B, gt_cap, A * T] bytes, gt_cap = most ground-truth boxes of one image.  Output per slot [image_pos[b], S]: the image's rows in
+ * (category, -score, row) order: category position (-1 = empty), score, rank inside (image, category), and a code per (area,
+ * threshold) for rank < max_det: 0 false positive, 1 true positive, 2 ignored.  Rewriting an image overwrites all its S slots.
+ * relnet_coco_accumulate = accumulate (cocoeval.py:274-375): one stable LSD radix sort of all slots with rank < max_det_host by
+ * (category, -score) in (image, slot) order (scores ordered as numpy's argsort(-score): -0.0 ties 0.0, NaN last), then per (category, area, maxDets) the tp / fp cumulative sums, recall, monotone
+ * precision sampled at rec_thr [R] (left searchsorted); -1 where npig [K, A] (int64) is 0.  max_dets [M] int32 device, M <= 4;
+ * precision [T, R, K, A, M], recall [T, K, A, M] float64.  workspace: relnet_coco_accumulate_workspace_bytes(n_slots, K, A * T). */
+int relnet_coco_match(const void* det, int det_dtype, const int* num_det, const int* image_pos, const int* class_to_cat,
+                      const int* gt_off, const double* gt_box, const unsigned char* gt_flags, const double* iou_thr,
+                      const double* area_rng, void* gtm_scratch, int* slot_cat, double* slot_score, int* slot_rank,
+                      void* slot_code, int B, int S_in, int S, int n_images, int n_classes, int K, int A, int T, int gt_cap,
+                      int max_det, int round_f32, int box_xywh, void* stream);
+long relnet_coco_accumulate_workspace_bytes(long n_slots, int K, int pairs);
+int relnet_coco_accumulate(const int* slot_cat, const double* slot_score, const int* slot_rank, const void* slot_code,
+                           long n_slots, const long long* npig, const double* rec_thr, const int* max_dets, double* precision,
+                           double* recall, void* workspace, long workspace_bytes, int K, int A, int T, int R, int M,
+                           int max_det_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,12 +102,7 @@ class coco(IMDB):
         """Write `results/detections_<set>_results.json` and, unless this is a test set, score it; returns
         (info_str, stats[12])."""
         assert ann_type == 'bbox'
-        res_folder = os.path.join(self.result_path, 'results')
-        os.makedirs(res_folder, exist_ok=True)
-        res_file = os.path.join(res_folder, 'detections_%s_results.json' % self.image_set)
-        results = self.results_list(detections)
-        with open(res_file, 'w') as f:
-            json.dump(results, f, sort_keys=True, indent=4)
+        results, res_file = self._write_results(detections)
         if 'test' in self.image_set:
             return 'results written to %s\n' % res_file, None
         gts = [a for anns in self._anns.values() for a in anns]
@@ -116,6 +111,25 @@ class coco(IMDB):
         stats = ev.summarize()
         info = self._detection_metrics(ev)
         return info, stats
+
+    def _write_results(self, detections):
+        res_folder = os.path.join(self.result_path, 'results')
+        os.makedirs(res_folder, exist_ok=True)
+        res_file = os.path.join(res_folder, 'detections_%s_results.json' % self.image_set)
+        results = self.results_list(detections)
+        with open(res_file, 'w') as f:
+            json.dump(results, f, sort_keys=True, indent=4)
+        return results, res_file
+
+    def evaluate_detections_device(self, ev, detections):
+        """evaluate_detections with the scores of a dataset/device_eval.py:DeviceCOCOeval `ev` that was given the same
+        detections: writes the same results json and returns the same (info_str, stats[12])."""
+        _, res_file = self._write_results(detections)
+        if 'test' in self.image_set:
+            return 'results written to %s\n' % res_file, None
+        ev.accumulate()
+        stats = ev.summarize()
+        return self._detection_metrics(ev), stats
 
     def _detection_metrics(self, ev):
         """coco.py:251-293: mean and per-category AP over IoU 0.50:0.95, area 'all', 100 detections."""

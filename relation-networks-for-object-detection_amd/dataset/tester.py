@@ -1,6 +1,8 @@
 """Test-time drivers of `relation_rcnn/core/tester.py` on the HIP detector.
 
   pred_eval            :163-307  loop over a TestLoader, collect all_boxes[cls][image] = [k,5], `imdb.evaluate_detections`.
+                                 device_eval=True: the detections stay on the device, are matched per batch by
+                                 dataset/device_eval.py:DeviceCOCOeval and copied to the host once at the end.
                                  The per-class threshold / (soft-)NMS / max_per_image steps (:244-277) run in the detector's
                                  post-processing kernels (relnet_class_nms / relnet_image_topk); learn-NMS outputs are
                                  thresholded as :231-242.
@@ -18,7 +20,11 @@ import torch
 def _class_lists(out, b, num_classes, scale):
     """detections [n,6] (class, score, x1,y1,x2,y2) of image b -> list over classes of [k,5] (x1,y1,x2,y2,score)."""
     n = int(out['num_detections'][b])
-    det = out['detections'][b, :n].detach().float().cpu().numpy()
+    return _split_classes(out['detections'][b, :n].detach().float().cpu().numpy(), num_classes)
+
+
+def _split_classes(det, num_classes):
+    """float32 rows [n,6] (class, score, x1,y1,x2,y2) -> list over classes of [k,5] (x1,y1,x2,y2,score)."""
     res = [np.zeros((0, 5), np.float32) for _ in range(num_classes)]
     for c in range(1, num_classes):
         rows = det[det[:, 0] == c]
@@ -27,40 +33,92 @@ def _class_lists(out, b, num_classes, scale):
     return res
 
 
-def pred_eval(detector, test_data, imdb, vis=False, thresh=1e-3, logger=None, device='cuda'):
+def pred_eval(detector, test_data, imdb, vis=False, thresh=1e-3, logger=None, device='cuda', device_eval=False):
     """Returns (info_str, stats, all_boxes).  `detector`: relnet_amd.detector.Detector (HAS_RPN graphs) or FPNDetector
-    (precomputed proposals from the loader).  The detector divides boxes by im_info[2] itself (tester.py:156)."""
+    (precomputed proposals from the loader).  The detector divides boxes by im_info[2] itself (tester.py:156).
+    device_eval: score on the device (DeviceCOCOeval): no explicit synchronisation and no device-to-host copy of the detections
+    per batch (the loader's own host-to-device uploads may still wait); all_boxes, the detections pickle, the results json, info
+    and stats are identical to the default path's."""
+    if device_eval:
+        return _pred_eval_device(detector, test_data, imdb, logger, device)
     num_images = imdb.num_images
     all_boxes = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
     t_net = []
     with torch.no_grad():
         for batch in test_data:
             t0 = time.time()
-            data, im_info = batch['data'].to(device), batch['im_info'].to(device)
-            if 'proposals' in batch:
-                nprop = batch.get('num_proposals')                       # TestLoader pads the images' proposal lists to one length
-                out = detector.forward(data, batch['proposals'].to(device), im_info,
-                                       num_proposals=None if nprop is None else nprop.to(device=device, dtype=torch.int32))
-            else:
-                detector.im_hw = (int(data.shape[2]), int(data.shape[3]))
-                out = detector.forward(data, im_info)
+            out = _run_detector(detector, batch, device)
             torch.cuda.synchronize()
             t_net.append(time.time() - t0)
             for b, idx in enumerate(batch['index']):
                 per_cls = _class_lists(out, b, imdb.num_classes, float(batch['im_info'][b, 2]))
                 for c in range(1, imdb.num_classes):
                     all_boxes[c][idx] = per_cls[c]
+    _dump_detections(imdb, all_boxes)
+    info, stats = imdb.evaluate_detections(all_boxes)
+    if logger:
+        logger.info('evaluate detections: \n{}'.format(info))
+        logger.info('net time per batch: %.4f s' % (float(np.mean(t_net)) if t_net else 0.0))
+    return info, stats, all_boxes
+
+
+def _dump_detections(imdb, all_boxes):
     for c in range(imdb.num_classes):
-        for i in range(num_images):
+        for i in range(imdb.num_images):
             if len(all_boxes[c][i]) == 0:
                 all_boxes[c][i] = np.zeros((0, 5), np.float32)
     det_file = os.path.join(imdb.result_path, imdb.name + '_detections.pkl')
     with open(det_file, 'wb') as f:
         pickle.dump(all_boxes, f, protocol=pickle.HIGHEST_PROTOCOL)
-    info, stats = imdb.evaluate_detections(all_boxes)
+
+
+def _run_detector(detector, batch, device):
+    data, im_info = batch['data'].to(device), batch['im_info'].to(device)
+    if 'proposals' in batch:
+        nprop = batch.get('num_proposals')                       # TestLoader pads the images' proposal lists to one length
+        return detector.forward(data, batch['proposals'].to(device), im_info,
+                                num_proposals=None if nprop is None else nprop.to(device=device, dtype=torch.int32))
+    detector.im_hw = (int(data.shape[2]), int(data.shape[3]))
+    return detector.forward(data, im_info)
+
+
+def _pred_eval_device(detector, test_data, imdb, logger, device):
+    """pred_eval(device_eval=True): each batch's detections are matched on the device as they come (no torch.cuda.synchronize,
+    no copy to the host) and kept there as float32 (pred_eval's .float()); one device-to-host copy at the end builds all_boxes."""
+    from .device_eval import DeviceCOCOeval
+    scoring = 'test' not in imdb.image_set                 # test sets only write results
+    ev, kept = None, []
+    t0 = time.time()
+    with torch.no_grad():
+        for batch in test_data:
+            out = _run_detector(detector, batch, device)
+            det, num = out['detections'], out['num_detections']
+            if scoring:
+                if ev is None:
+                    ev = DeviceCOCOeval(imdb, slots=det.shape[1], device=device)
+                ev.add(det, num, batch['index'])
+            kept.append((list(batch['index']), det.to(torch.float32, copy=True), num.to(torch.int32, copy=True)))
+    all_boxes = [[[] for _ in range(imdb.num_images)] for _ in range(imdb.num_classes)]
+    if kept:
+        width = max(d.shape[1] for _, d, _ in kept)
+        dets = torch.cat([torch.nn.functional.pad(d, (0, 0, 0, width - d.shape[1])) for _, d, _ in kept]).cpu().numpy()
+        nums = torch.cat([n for _, _, n in kept]).cpu().numpy()
+        row = 0
+        for idx, _, _ in kept:
+            for i in idx:
+                per_cls = _split_classes(dets[row, :nums[row]], imdb.num_classes)
+                for c in range(1, imdb.num_classes):
+                    all_boxes[c][i] = per_cls[c]
+                row += 1
+    t_net = time.time() - t0
+    _dump_detections(imdb, all_boxes)
+    if ev is None:
+        info, stats = imdb.evaluate_detections(all_boxes)
+    else:
+        info, stats = imdb.evaluate_detections_device(ev, all_boxes)
     if logger:
         logger.info('evaluate detections: \n{}'.format(info))
-        logger.info('net time per batch: %.4f s' % (float(np.mean(t_net)) if t_net else 0.0))
+        logger.info('net time per batch: %.4f s' % (t_net / max(len(kept), 1)))
     return info, stats, all_boxes
 
 

@@ -153,6 +153,9 @@ _SIGNATURES = {
                                        C.c_double, C.c_double, _i, _i, C.c_ulonglong, _vp, _vp]),
     'relnet_box_annotator_ohem': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'relnet_nms_multi_target': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    'relnet_coco_match': (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 12 + [_vp]),
+    'relnet_coco_accumulate_workspace_bytes': (C.c_long, [_l, _i, _i]),
+    'relnet_coco_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _l] + [_i] * 6 + [_vp]),
 }
 
 

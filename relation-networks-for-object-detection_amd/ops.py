@@ -478,6 +478,52 @@ def image_topk(dets, counts, max_per_image=100, max_out=None):
 
 
 # ---------------------------------------------------------------------------------------
+# COCO bbox evaluation (csrc/cocoeval.hip; the host definition is dataset/cocoeval.py)
+# ---------------------------------------------------------------------------------------
+def coco_match(det, num_det, image_pos, class_to_cat, gt_off, gt_box, gt_flags, iou_thr, area_rng, slot_cat, slot_score,
+               slot_rank, slot_code, gt_cap, max_det, round_f32=False, box_xywh=False):
+    """Greedy matching of one batch: det [B,S_in,6] float32 / float64 (class, score, box), num_det [B] int32, image_pos [B] int32
+    (distinct positions in the evaluated image list).  Writes the slots [n_images, S] of every batch image: slot_cat int32,
+    slot_score float64, slot_rank int32, slot_code uint8 [n_images, S, A*T].  No host synchronisation."""
+    _chk(det, num_det, image_pos, class_to_cat, gt_off, gt_box, gt_flags, iou_thr, area_rng, slot_cat, slot_score, slot_rank, slot_code)
+    if det.dtype not in (torch.float32, torch.float64):
+        raise TypeError("coco_match: detections must be float32 or float64, got %s" % det.dtype)
+    B, S_in = det.shape[:2]
+    n_images, S = slot_cat.shape
+    T, A = iou_thr.numel(), area_rng.shape[0]
+    assert det.shape[2] == 6 and det.is_contiguous() and num_det.dtype == torch.int32 and image_pos.dtype == torch.int32
+    assert num_det.numel() == B and image_pos.numel() == B and slot_code.shape == (n_images, S, A * T)
+    assert gt_off.dtype == torch.int32 and (gt_off.numel() - 1) % n_images == 0 and class_to_cat.dtype == torch.int32
+    K = (gt_off.numel() - 1) // n_images
+    gtm = torch.empty((B, max(gt_cap, 1), A * T), device=det.device, dtype=torch.uint8)
+    _lib.call('relnet_coco_match', det.data_ptr(), int(det.dtype == torch.float64), num_det.data_ptr(), image_pos.data_ptr(),
+              class_to_cat.data_ptr(), gt_off.data_ptr(), gt_box.data_ptr(), gt_flags.data_ptr(), iou_thr.data_ptr(),
+              area_rng.data_ptr(), gtm.data_ptr(), slot_cat.data_ptr(), slot_score.data_ptr(), slot_rank.data_ptr(),
+              slot_code.data_ptr(), B, S_in, S, n_images, class_to_cat.numel(), K, A, T, int(gt_cap), int(max_det),
+              int(bool(round_f32)), int(bool(box_xywh)), _stream())
+
+
+def coco_accumulate(slot_cat, slot_score, slot_rank, slot_code, npig, rec_thr, max_dets, max_det):
+    """Stable device sort of the slots by (category, -score) and the accumulation: npig [K,A] int64, rec_thr [R] float64,
+    max_dets [M] int32 (device), max_det = the largest of them.  -> precision [T,R,K,A,M], recall [T,K,A,M] float64."""
+    _chk(slot_cat, slot_score, slot_rank, slot_code, npig, rec_thr, max_dets)
+    n = slot_cat.numel()
+    K, A = npig.shape
+    T, R, M = slot_code.shape[-1] // A, rec_thr.numel(), max_dets.numel()
+    assert npig.dtype == torch.int64 and rec_thr.dtype == torch.float64 and max_dets.dtype == torch.int32
+    ws_bytes = _lib.load().relnet_coco_accumulate_workspace_bytes(n, K, A * T)
+    if ws_bytes < 0:
+        raise _lib.RelnetError("relnet_coco_accumulate_workspace_bytes: bad shape (%d slots, %d categories)" % (n, K))
+    ws = torch.empty((ws_bytes,), device=slot_cat.device, dtype=torch.uint8)
+    precision = torch.empty((T, R, K, A, M), device=slot_cat.device, dtype=torch.float64)
+    recall = torch.empty((T, K, A, M), device=slot_cat.device, dtype=torch.float64)
+    _lib.call('relnet_coco_accumulate', slot_cat.data_ptr(), slot_score.data_ptr(), slot_rank.data_ptr(), slot_code.data_ptr(), n,
+              npig.data_ptr(), rec_thr.data_ptr(), max_dets.data_ptr(), precision.data_ptr(), recall.data_ptr(), ws.data_ptr(),
+              ws_bytes, K, A, T, R, M, int(max_det), _stream())
+    return precision, recall
+
+
+# ---------------------------------------------------------------------------------------
 # NHWC convolution (implicit GEMM on the bf16 MFMA kernel)
 # ---------------------------------------------------------------------------------------
 def pack_conv_weight(w_oihw, dtype=torch.bfloat16, device='cuda'):
