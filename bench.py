@@ -2,6 +2,7 @@
 """Headline benchmark: images/s of the relation-network detector forward pass.
 
   python bench.py --gpus N --steps K --warmup W         (N>1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W --full  (+ every side figure below)
 
 One step = one pass of the hot path over a batch of `--batch` (default 108) synthetic 600x1000 images per
 GPU: ResNet-101 conv1..conv5 + RPN -> proposal (300 rois) -> ROIPooling -> 2FC + 2 relation
@@ -10,7 +11,10 @@ modules (16 heads, d=1024) -> cls/bbox -> decode -> per-class soft-NMS -> top-10
 Images are independent units: ranks share nothing on the data path (weak scaling, no
 collective); the barrier + max-over-ranks timing is the only communication.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line.  With --full
+the JSON line also carries (each side figure runs after the timed steps; --no-<figure> leaves one out)
+  in_flight     the same K steps with --in-flight batches in flight (N = 1 only).
+  kernels_ms    per-kernel HIP-event times of an eager re-run of the step, with `conv_roofline` per convolution shape.
   roofline      the relation-attention kernel (north_star's named kernel), stated on the roof that bounds it: HBM.  `achieved` =
                 algorithmic bytes per launch (SURVEY.md 8d with the geometry fused: 3.12 MB per image) / launch duration (HIP events on
                 the launching stream), `peak` 8000 GB/s, `traffic` = PMC bytes; `mfma_frac_as_written` (3.13 GFLOP per module-image as
@@ -24,6 +28,8 @@ The JSON line also carries
   train         BASELINE configs[2] on the same N GPUs: training step of relation + learn-NMS end2end with ONE
                 summed RCCL all-reduce of the 68.3 M gradients per step (the path the 1 -> 8 GPU scaling target
                 is stated on; `value` stays the inference figure so that the N = 1..8 curve is one metric).
+  other_configs BASELINE configs[3] / configs[4] inference and training rates (N = 1 only).
+A --train line with N > 1 carries its per-bucket communication timing with --full only.
 """
 import argparse
 import contextlib
@@ -437,7 +443,7 @@ def bench_train(a, rank, world, D, emit=True, fatal=True):
         if emit and rank == 0 and getattr(a, 'dump_outputs', None):      # (outside the timed region)
             dumped = dump_outputs({'step': out, 'weights_master': tr.W.master}, a.dump_outputs)
         comm = None
-        if world > 1:       # self-diagnosis of the N > 1 line (verdict r05 item 8), OUTSIDE the timed region: the same steps again with HIP
+        if world > 1 and a.full:       # self-diagnosis of the N > 1 line (verdict r05 item 8), OUTSIDE the timed region: the same steps again with HIP
             tr.comm_timing = []               # events around every bucket's wait -> exposed communication per step and per bucket
             n_c = min(a.steps, 5)
             for _ in range(n_c):
@@ -500,7 +506,7 @@ def bench_train(a, rank, world, D, emit=True, fatal=True):
                        'images_per_gpu_per_step': B, 'launch': 'eager' if a.no_graph else ('hipGraph replay (forward+backward in %d segments cut at the gradient buckets)' % len(graph.segments) if len(graph.segments) > 1 else 'hipGraph replay (forward+backward as one graph: one rank, no bucket exchange to cut for)'),
                        'parallelism': 'dp%d (RCCL all-reduce SUM)' % world, 'lr': cfg.lr,
                        'lr_rule': 'yaml lr %g x min(1, 16 / images summed per step over all ranks)' % yaml_lr},
-            'communication': comm if comm is not None else 'single rank: no collective',
+            'communication': comm if comm is not None else ('single rank: no collective' if world == 1 else 'not measured (--full)'),
             'losses': {k: float(out[k]) for k in ('bbox_loss', 'rpn_bbox_loss', 'nms_pos_loss', 'nms_neg_loss') if k in out},
             'weights_finite_on_all_ranks': bool(ok)}
         if dumped is not None:
@@ -517,6 +523,10 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline figure, also run every side figure (in-flight rate, per-kernel times and rooflines, parity '
+                         'against the CPU oracle, batch sweep, CPU baseline, training rates, other configs; the N > 1 communication '
+                         'timing of --train); the --no-<figure> options below leave single ones out')
     ap.add_argument('--batch', type=int, default=None, help='images per GPU per step (default 108 for the headline graph, 54 for the other inference graphs; 8 with --train)')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
     ap.add_argument('--no-overlap', action='store_true', help='A/B: RPN head + proposal on the main stream instead of beside res5')
@@ -533,13 +543,13 @@ def main():
     ap.add_argument('--no-parity', action='store_true')
     ap.add_argument('--no-batch-sweep', action='store_true')
     ap.add_argument('--no-train-line', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the configs[3] / configs[4] (+ learn-NMS) side figures of the default line')
+    ap.add_argument('--no-other-configs', action='store_true', help='skip the configs[3] / configs[4] (+ learn-NMS) side figures of the --full line')
     ap.add_argument('--cpu-threads', type=int, default=32)
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--stem', default='hip', choices=['hip', 'hip3', 'miopen'], help="stem: 'hip' one fused conv1 + ReLU + pool1 kernel, 'hip3' the three-launch form, 'miopen' library 7x7")
     ap.add_argument('--no-graph', action='store_true', help='time eager launches instead of hipGraph replays')
-    ap.add_argument('--in-flight', type=int, default=3, help='side figures of the inference line: batches in flight (captured steps with the RPN branch in line, each on its own stream, submitted round-robin; 1 = none). `value` is always the one-at-a-time rate')
-    ap.add_argument('--shapes', action='store_true', help='print per-shape GEMM/conv times to stderr')
+    ap.add_argument('--in-flight', type=int, default=3, help='side figures of the --full inference line: batches in flight (captured steps with the RPN branch in line, each on its own stream, submitted round-robin; 1 = none). `value` is always the one-at-a-time rate')
+    ap.add_argument('--shapes', action='store_true', help='with --full: print per-shape GEMM/conv times to stderr')
     ap.add_argument('--head-init-std', type=float, default=0.05,
                     help='std of the random cls_score / bbox_pred weights (reference init: 0.01, which makes every class posterior '
                          '~1/81 and the parity block blind to the head; the cost of the step does not depend on it)')
@@ -669,7 +679,7 @@ def main():
         # detector instance (own buffers), a second resident batch, each step captured on its own stream, steps submitted round-robin.
         # `value` stays the one-at-a-time rate of rounds 1-5
         elapsed_fl, n_flight, flight_err = None, 1, None
-        if graph is not None and a.in_flight > 1 and world == 1:      # (one rank only: a side figure must not be able to leave other ranks in a barrier)
+        if a.full and graph is not None and a.in_flight > 1 and world == 1:      # (one rank only: a side figure must not be able to leave other ranks in a barrier)
             del graph                 # (its executable graph holds runtime streams: with it alive the graphs below measured no overlap at all)
             graph = True
             torch.cuda.synchronize()
@@ -697,7 +707,7 @@ def main():
                 torch.cuda.synchronize()
         # per-kernel durations: the same step launched eagerly with HIP events around every C-ABI
         # launch (events cannot be timed inside a captured graph); same inputs, same stream
-        timer = None if a.no_kernel_timing else KernelTimer()
+        timer = KernelTimer() if (a.full and not a.no_kernel_timing) else None
         if timer is not None:
             lib.timing_hook = timer
             for _ in range(min(a.steps, 5)):
@@ -729,15 +739,15 @@ def main():
                                       'learn-NMS (first_n %d, class_thresh %g, 80 classes)' % (cfg.first_n, cfg.learn_nms_class_thresh) if a.learn_nms else 'soft-NMS(0.6)'),
                        'images_per_gpu_per_step': a.batch,
                        'launch': 'eager' if a.no_graph else 'hipGraph replay', 'batches_in_flight': 1, 'parallelism': 'replicas x%d (no data-path collective)' % world,
-                       'cross_round_figure': "`value` is quoted at %d images per GPU per step (the default since the end of round 4); rounds 1-3 quoted 54: compare those with batch_sweep['54']" % a.batch,
+                       'cross_round_figure': "`value` is quoted at %d images per GPU per step (the default since the end of round 4); rounds 1-3 quoted 54: compare those with batch_sweep['54'] (--full)" % a.batch,
                        'ranks_seen_by_rccl': ranks_seen, 'head_init_std': a.head_init_std,
                        'precision': 'bf16 operands, fp32 accumulation (fp16 only for the log2 geometry bias read by the attention kernel); BASELINE '
                                     'configs[4] words its FPN run as "fp16": it is run with bf16 operands here -- the fp16 twin of the GEMM kernel was '
                                     'measured 8-13 % SLOWER on gfx950 (same 8-pass MFMA, power-limited pipes; profiles/r05_notes/fp16_vs_bf16.txt)',
                        'scaling_figure': ('`value` is the replica-inference rate (no data-path collective: linear by construction). The 1 -> N GPU '
                                           'scaling north_star targets is the TRAINING step with its RCCL gradient all-reduce: read `train.value` '
-                                          '(and other_configs.*_training.value) across N') if world > 1 else
-                                         'single GPU; at N > 1 the data-parallel scaling figure is train.value (training step incl. the RCCL all-reduce)',
+                                          'of a --full line (and other_configs.*_training.value) across N') if world > 1 else
+                                         'single GPU; at N > 1 the data-parallel scaling figure is train.value of a --full line (training step incl. the RCCL all-reduce)',
                        **({'one_device_test': 'all %d ranks share cuda:0 and exchange over gloo (RELNET_BENCH_ONE_DEVICE): a code-path check, NOT a multi-GPU number' % world} if one_dev else {})},
         }
         if dumped is not None:
@@ -824,21 +834,21 @@ def main():
                 iso = attention_isolated(a.batch, n_rois, tdt)           # kernel alone: median of 100 launches
                 res['roofline'].update(isolated_median_ms=iso, isolated_frac=algo_bytes / (iso * 1e-3) / 8e12)
         plain = not (a.dcn or a.fpn or a.learn_nms)
-        if world == 1 and plain and not a.no_parity and a.dtype == 'bf16':
+        if a.full and world == 1 and plain and not a.no_parity and a.dtype == 'bf16':
             # the timed configuration itself (same detector object, same batch) checked stage by stage against the oracle
             from oracle import parity as OPAR
             res['parity'] = OPAR.stagewise(det, data, im_info, params, images=range(min(a.parity_images, a.batch)),
                                            relation=not a.no_relation)
-        if world == 1 and plain and not a.no_batch_sweep:
+        if a.full and world == 1 and plain and not a.no_batch_sweep:
             res['batch_sweep'] = {'note': 'images/s of the same step at other images-per-GPU-per-step settings (hipGraph replay); '
                                           '1 = the reference protocol (BATCH_IMAGES: 1, SURVEY 8d)'}
             for bsz in (1, 8, 54):
                 if bsz == a.batch:
                     continue
                 res['batch_sweep'][str(bsz)] = _replay_rate(det, bsz, a, D, make_det=make_det if a.in_flight > 1 else None, n_flight=a.in_flight)
-        if world == 1 and not a.no_cpu_baseline and not a.dcn and not a.fpn:      # the CPU port of the DCN graph is parity-only (slow)
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.dcn and not a.fpn:      # the CPU port of the DCN graph is parity-only (slow)
             res['cpu_baseline'] = cpu_baseline(params, relation=not a.no_relation, images=a.cpu_images, threads=a.cpu_threads)
-    if plain_graph and not a.no_train_line:
+    if a.full and plain_graph and not a.no_train_line:
         # BASELINE configs[2] (relation + learn-NMS end2end TRAINING, one summed RCCL all-reduce per step) on the same N GPUs:
         # the data-parallel path north_star's scaling target is stated on; every rank takes part in the collective
         del det
@@ -865,9 +875,9 @@ def main():
             if tr1 is not None and 'error' not in tr1:
                 res['train']['at_1_image_per_gpu']['note'] = ("the reference's own protocol: BATCH_IMAGES 1 per device (cfgs/..._rcnn_end2end_relation_"
                                                                "learn_nms_8epoch.yaml:80); ~380 launches of 4 - 37 us on 2 394-pixel maps, latency bound")
-    if plain_graph and not a.no_other_configs and world > 1 and rank == 0:
-        res['other_configs'] = 'single-GPU side figures (configs[3] / configs[4] inference and training rates): run `python bench.py` with --gpus 1'
-    if plain_graph and not a.no_other_configs and world == 1:
+    if a.full and plain_graph and not a.no_other_configs and world > 1 and rank == 0:
+        res['other_configs'] = 'single-GPU side figures (configs[3] / configs[4] inference and training rates): run `python bench.py --full` with --gpus 1'
+    if a.full and plain_graph and not a.no_other_configs and world == 1:
         if 'det' in locals():
             del det
         torch.cuda.empty_cache()

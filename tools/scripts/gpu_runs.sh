@@ -2,7 +2,7 @@
 # The gpurun command lines behind the numbers in DESIGN.md / profiles/ (one parametrised script instead of one scratch file per run):
 #     gpurun --timeout 2400 -- 'bash tools/scripts/gpu_runs.sh <what> [args]'        outputs under gpurun_out/r04_<what>/  (or TAG=...)
 #   suite      whole GPU test suite
-#   bench      the driver's default line (python bench.py), full JSON
+#   bench      the benchmark with every side figure (python bench.py --full), full JSON
 #   ab KNOB    same-box A/B of the default step with a kernel-selection knob off / on, twice
 #              (KNOB = RELNET_GEMM_ASM | RELNET_INPLACE_EXPAND | RELNET_STAGE_SPLIT=4:2 | RELNET_GEMM_KORDER)
 #   tiles T,.. parity tests of the forced tiles, then their per-layer times at 54 images (tools/bench_tiles.py), e.g. `tiles 8,18,19`
@@ -19,7 +19,7 @@ F="--no-cpu-baseline --no-train-line --no-other-configs --no-parity --no-batch-s
 line() { python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{\"metric')][-1]); print(sys.argv[2], round(d['value'],1), 'img/s', round(d['ms_per_step'],3), 'ms', d['config'].get('images_per_gpu_per_step'))" "$1" "$2" 2>/dev/null || echo "$2 FAILED"; }
 case $WHAT in
   suite) ( time timeout 1800 python -m pytest tests -x -q -m gpu ) > $O/pytest_gpu.log 2>&1; tail -6 $O/pytest_gpu.log ;;
-  bench) ( time python bench.py ) > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err; line $O/bench.json default ;;
+  bench) ( time python bench.py --full ) > $O/bench.json 2> $O/bench.err; tail -4 $O/bench.err; line $O/bench.json default ;;
   ab)
     KNOB=$1; NAME=${KNOB%%=*}; ON=${KNOB#*=}; [ "$ON" = "$KNOB" ] && ON=1
     export RELNET_DEBUG_KNOBS=1
