@@ -707,6 +707,23 @@ int relnet_coco_accumulate(const int* slot_cat, const double* slot_score, const 
                            double* recall, void* workspace, long workspace_bytes, int K, int A, int T, int R, int M,
                            int max_det_host, void* stream);
 
+/* ---- Proposal recall (csrc/recall.hip), bit-identical to dataset/recall.py = evaluate_recall of lib/dataset/imdb.py:274-370 ----
+ * relnet_recall_match: greedy cover of one batch of candidate lists against the valid ground truth, one workgroup per (batch
+ * image, area range).  boxes: float32 x1 y1 x2 y2 of candidate i of batch image b at boxes + b * box_bs + i * box_rs (floats);
+ * scores [B, P] float32 or null, num_valid [B] int32 or null (all P); scale [B] float32 or null: boxes divided by it in fp32
+ * first; with scores, only candidates with score > thresh are kept (list order kept).  image_pos [B] int32.  Ground truth:
+ * CSR gt_off [n_images + 1] int32, gt_box [n_gt, 4] float64 in roidb order, gt_mask [n_gt] bit a = area in range a (computed
+ * by the host in the roidb's dtype: coco's uint16 areas wrap).  thresholds [T] float64, area_rng [A, 2] float64 half-open.
+ * Ties: the lowest gt index among equal column maxima, then the lowest candidate index of that column.  Accumulated with int64
+ * atomics: hits [A, T], num_pos [A], area_count [A - 1] (candidate areas in fp32, ranges 1..A-1).  Per image: n_cand (kept
+ * candidates), added (+1), overlaps [n_images, A, gt_cap] float64 (recorded values in round order) unless null.
+ * P <= 2048, gt_cap <= 256, A <= 8, T <= 256: larger is refused before launch. */
+int relnet_recall_match(const float* boxes, long box_bs, long box_rs, const float* scores, const int* num_valid,
+                        const float* scale, float thresh, const int* image_pos, const int* gt_off, const double* gt_box,
+                        const unsigned char* gt_mask, const double* thresholds, const double* area_rng,
+                        unsigned long long* hits, unsigned long long* num_pos, unsigned long long* area_count, int* n_cand,
+                        int* added, double* overlaps, int B, int P, int n_images, int A, int T, int gt_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,14 @@ class IMDB(object):
         self.image_set_index = list(self.image_set_index) + list(self.image_set_index)
         return roidb
 
+    def evaluate_recall(self, roidb, candidate_boxes=None, thresholds=None):
+        """Proposal recall at IoU thresholds (default 0.50:0.95) and average recall for seven gt-area ranges
+        (`imdb.py:274-370`); returns the same all_log_info string.  candidate_boxes: per image [n, 4+] (a `_rpn.pkl` list);
+        None uses the roidb's non-gt rows.  The arithmetic and its quirks are in dataset/recall.py, which also returns the
+        arrays; dataset/device_recall.py computes the same on the device."""
+        from .recall import evaluate_recall
+        return evaluate_recall(roidb, self.num_images, candidate_boxes, thresholds)[0]
+
     @staticmethod
     def merge_roidbs(a, b):
         """Joins, image by image, the rois of `b` below those of `a` (proposals + ground truth, `imdb.py:382-400`);

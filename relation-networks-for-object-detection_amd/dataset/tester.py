@@ -8,6 +8,9 @@
                                  thresholded as :231-242.
   generate_proposals   :63-126   RPN-only pass, boxes mapped back to the original image scale, written as the
                                  `<name>_rpn.pkl` list the precomputed-proposal training reads (imdb.load_rpn_data).
+                                 device_recall=True: the rois stay on the device and are scored per batch by
+                                 dataset/device_recall.py:DeviceRecall; one device-to-host copy at the end builds the list.
+  test_rpn             function/test_rpn.py:25-76  generate_proposals + imdb.evaluate_recall (or DeviceRecall).
 """
 import os
 import pickle
@@ -122,9 +125,13 @@ def _pred_eval_device(detector, test_data, imdb, logger, device):
     return info, stats, all_boxes
 
 
-def generate_proposals(detector, test_data, imdb, thresh=0.0, device='cuda', save=True):
+def generate_proposals(detector, test_data, imdb, thresh=0.0, device='cuda', save=True, device_recall=False):
     """tester.py:63-126: per image [n,5] = (x1,y1,x2,y2 at the ORIGINAL scale, rpn score); returns the list and writes
-    `<rpn_path>/rpn_data/<name>_rpn.pkl` (+ `_full_rpn.pkl` when thresh > 0)."""
+    `<rpn_path>/rpn_data/<name>_rpn.pkl` (+ `_full_rpn.pkl` when thresh > 0).
+    device_recall=True: returns (list, DeviceRecall) -- every batch's rois are scored on the device as they come (scaled and
+    thresholded there as below, no copy to the host) and copied to the host once at the end; the list is the same."""
+    if device_recall:
+        return _generate_proposals_device(detector, test_data, imdb, thresh, device, save)
     from ..operator_py.proposal import propose_batch
     imdb_boxes, original = [None] * imdb.num_images, [None] * imdb.num_images
     c = detector.cfg
@@ -146,3 +153,66 @@ def generate_proposals(detector, test_data, imdb, thresh=0.0, device='cuda', sav
         if thresh > 0:
             imdb.save_rpn_data(original, full=True)
     return imdb_boxes
+
+
+def _rpn_batch(detector, batch, device):
+    from ..operator_py.proposal import propose_batch
+    c = detector.cfg
+    data, im_info = batch['data'].to(device), batch['im_info'].to(device)
+    f = detector.backbone.forward(data)
+    return propose_batch(f['rpn_cls_score'].float(), f['rpn_bbox_pred'].float(), im_info, detector.anchors, c.feat_stride,
+                         c.rpn_pre_nms_top_n, c.rpn_post_nms_top_n, c.rpn_nms_thresh, c.rpn_min_size,
+                         im_hw=(int(data.shape[2]), int(data.shape[3])), softmax_pairs=True), im_info
+
+
+def _generate_proposals_device(detector, test_data, imdb, thresh, device, save):
+    """generate_proposals(device_recall=True): the proposal list is built from one device-to-host copy of every batch's rois
+    and scores with the default path's numpy expressions, so it is identical to it."""
+    from .device_recall import DeviceRecall
+    ev = DeviceRecall(imdb, device=device)
+    kept = []
+    with torch.no_grad():
+        for batch in test_data:
+            (rois, scores), im_info = _rpn_batch(detector, batch, device)
+            scores = scores.reshape(rois.shape[0], rois.shape[1])
+            ev.add(rois[:, :, 1:], None, batch['index'], scores=scores, thresh=thresh, scale=im_info[:, 2])
+            kept.append((list(batch['index']), [float(batch['im_info'][b, 2]) for b in range(len(batch['index']))],
+                         rois[:, :, 1:].to(torch.float32, copy=True), scores.to(torch.float32, copy=True)))
+    imdb_boxes, original = [None] * imdb.num_images, [None] * imdb.num_images
+    if kept:
+        width = max(r.shape[1] for _, _, r, _ in kept)
+        rois = torch.cat([torch.nn.functional.pad(r, (0, 0, 0, width - r.shape[1])) for _, _, r, _ in kept]).cpu().numpy()
+        scores = torch.cat([torch.nn.functional.pad(s, (0, width - s.shape[1])) for _, _, _, s in kept]).cpu().numpy()
+        row = 0
+        for idx, scales, r, _ in kept:
+            n = r.shape[1]
+            for i, scale in zip(idx, scales):
+                boxes = rois[row, :n] / scale
+                dets = np.hstack((boxes, scores[row, :n].reshape(-1, 1))).astype(np.float32)
+                original[i] = dets
+                imdb_boxes[i] = dets[np.where(dets[:, 4] > thresh)[0], :]
+                row += 1
+    assert all(x is not None for x in imdb_boxes), 'calculations not complete'
+    if save:
+        imdb.save_rpn_data(imdb_boxes)
+        if thresh > 0:
+            imdb.save_rpn_data(original, full=True)
+    return imdb_boxes, ev
+
+
+def test_rpn(detector, test_data, imdb, thresh=0.0, device='cuda', device_eval=False, logger=None):
+    """function/test_rpn.py:25-76: proposals of every test image (generate_proposals, which writes `<name>_rpn.pkl`) scored by
+    imdb.evaluate_recall against imdb.gt_roidb(); returns all_log_info.  device_eval=True scores them on the device
+    (DeviceRecall) and returns the same string.
+    The reference builds its network with sym.get_symbol_rpn, which none of its shipped symbol files defines; the RPN here is
+    the detector's backbone RPN head + propose_batch, as generate_proposals uses it.  `test_data` is a non-shuffled
+    TestLoader(imdb.gt_roidb(), cfg, has_rpn=True)."""
+    if device_eval:
+        _, ev = generate_proposals(detector, test_data, imdb, thresh=thresh, device=device, device_recall=True)
+        all_log_info = ev.summarize()[0]
+    else:
+        imdb_boxes = generate_proposals(detector, test_data, imdb, thresh=thresh, device=device)
+        all_log_info = imdb.evaluate_recall(imdb.gt_roidb(), candidate_boxes=imdb_boxes)
+    if logger:
+        logger.info(all_log_info)
+    return all_log_info

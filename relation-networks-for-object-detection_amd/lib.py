@@ -156,6 +156,7 @@ _SIGNATURES = {
     'relnet_coco_match': (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 12 + [_vp]),
     'relnet_coco_accumulate_workspace_bytes': (C.c_long, [_l, _i, _i]),
     'relnet_coco_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _l] + [_i] * 6 + [_vp]),
+    'relnet_recall_match': (C.c_int, [_vp, _l, _l, _vp, _vp, _vp, _f] + [_vp] * 12 + [_i] * 6 + [_vp]),
 }
 
 

@@ -524,6 +524,55 @@ def coco_accumulate(slot_cat, slot_score, slot_rank, slot_code, npig, rec_thr, m
 
 
 # ---------------------------------------------------------------------------------------
+# Proposal recall (csrc/recall.hip; the host definition is dataset/recall.py)
+# ---------------------------------------------------------------------------------------
+RECALL_MAX_CANDIDATES = 2048
+RECALL_MAX_GT = 256
+RECALL_MAX_THRESHOLDS = 256
+
+
+def recall_match(boxes, image_pos, gt_off, gt_box, gt_mask, thresholds, area_rng, hits, num_pos, area_count, n_cand, added,
+                 gt_cap, num_valid=None, scores=None, thresh=0.0, scale=None, overlaps=None):
+    """Greedy proposal cover of one batch: boxes [B,P,4] float32 (any batch / row strides, x1 y1 x2 y2 contiguous), image_pos
+    [B] int32, num_valid [B] int32, scores [B,P] float32 (kept: score > float32(thresh)), scale [B] float32 (boxes / scale in
+    fp32).  Accumulates hits [A,T], num_pos [A], area_count [A-1] int64 and writes n_cand / added [n_images] int32 and, when
+    given, overlaps [n_images, A, gt_cap] float64.  No host synchronisation."""
+    _chk(boxes, image_pos, gt_off, gt_box, gt_mask, thresholds, area_rng, hits, num_pos, area_count, n_cand, added, num_valid,
+         scores, scale, overlaps)
+    if boxes.dtype != torch.float32 or boxes.dim() != 3 or boxes.shape[2] != 4 or boxes.stride(2) != 1:
+        raise ValueError("recall_match: boxes must be float32 [B, P, 4] with contiguous rows, got %s %s" % (boxes.dtype, tuple(boxes.shape)))
+    B, P = boxes.shape[:2]
+    if P > RECALL_MAX_CANDIDATES:
+        raise ValueError("recall_match: %d candidates per image, the kernel takes at most %d" % (P, RECALL_MAX_CANDIDATES))
+    if gt_cap > RECALL_MAX_GT:
+        raise ValueError("recall_match: %d ground-truth boxes in one image, the kernel takes at most %d" % (gt_cap, RECALL_MAX_GT))
+    A, T, n_images = area_rng.shape[0], thresholds.numel(), n_cand.numel()
+    if T > RECALL_MAX_THRESHOLDS or not 1 < A <= 8:
+        raise ValueError("recall_match: %d thresholds (at most %d) and %d area ranges (2..8)" % (T, RECALL_MAX_THRESHOLDS, A))
+    assert image_pos.dtype == torch.int32 and image_pos.numel() == B and gt_off.dtype == torch.int32 and gt_off.numel() == n_images + 1
+    assert gt_box.dtype == torch.float64 and gt_mask.dtype == torch.uint8 and thresholds.dtype == torch.float64
+    assert area_rng.dtype == torch.float64 and area_rng.shape == (A, 2) and added.dtype == torch.int32 and n_cand.dtype == torch.int32
+    assert hits.dtype == num_pos.dtype == area_count.dtype == torch.int64
+    assert hits.shape == (A, T) and num_pos.shape == (A,) and area_count.shape == (A - 1,)
+    assert all(t.is_contiguous() for t in (hits, num_pos, area_count, n_cand, added, gt_off, gt_box, gt_mask, thresholds, area_rng))
+    if num_valid is not None:
+        assert num_valid.dtype == torch.int32 and num_valid.numel() == B
+    if scores is not None:
+        assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == B * P
+    if scale is not None:
+        assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == B
+    if overlaps is not None:
+        assert overlaps.dtype == torch.float64 and overlaps.is_contiguous() and overlaps.shape == (n_images, A, gt_cap)
+    if B == 0:
+        return
+    _lib.call('relnet_recall_match', boxes.data_ptr() if P else 0, boxes.stride(0), boxes.stride(1), _ptr(scores),
+              _ptr(num_valid), _ptr(scale), float(thresh), image_pos.data_ptr(), gt_off.data_ptr(), gt_box.data_ptr(),
+              gt_mask.data_ptr(), thresholds.data_ptr(), area_rng.data_ptr(), hits.data_ptr(), num_pos.data_ptr(),
+              area_count.data_ptr(), n_cand.data_ptr(), added.data_ptr(), _ptr(overlaps), B, P, n_images, A, T, int(gt_cap),
+              _stream())
+
+
+# ---------------------------------------------------------------------------------------
 # NHWC convolution (implicit GEMM on the bf16 MFMA kernel)
 # ---------------------------------------------------------------------------------------
 def pack_conv_weight(w_oihw, dtype=torch.bfloat16, device='cuda'):
