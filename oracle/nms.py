@@ -9,6 +9,11 @@
                   tests/test_gpu_refcuda.py the product's `_nms` to the reference's `_nms`.
   * `py_nms`   -- lib/nms/nms.py:45-82 (keep while ovr <= thresh).   Pinned.
   * `soft_nms` -- lib/nms/nms.py:85-141 (gaussian rescoring, re-sort each step). Pinned.
+
+Ties (ONE rule, stated in DESIGN.md "Tolerances" and followed by every kernel, this oracle and the nms/ twins): among
+exactly equal scores the LARGER ORIGINAL INDEX comes first -- in the proposal sort, in `gpu_nms` / `cpu_nms` / `nms`, and at
+EVERY pick of `soft_nms` (current scores compared, original indices break the tie; no order history).  The reference's
+`argsort()[::-1]` is numpy's unstable default sort and fixes no order among equals, so the rule is this project's own.
 """
 import numpy as np
 
@@ -19,8 +24,9 @@ def argsort_desc(scores):
     """Descending order exactly as the reference spells it: `argsort()[::-1]`
     (proposal.py:140, gpu_nms.pyx:28, nms.py:62).  numpy's default sort is not
     stable, so the order of exactly tied scores is unspecified in the reference;
-    test inputs are tie-free, and the HIP path documents its own tie rule
-    (ties -> higher original index first, i.e. the reversed stable sort)."""
+    the project's rule (ties -> higher original index first) is the
+    reversed stable sort, and tests/test_gpu_ties.py holds the HIP kernels to it on
+    tied inputs (quantised scores, all-equal scores, -inf rows)."""
     return np.argsort(scores, kind='stable')[::-1]
 
 
@@ -71,6 +77,30 @@ def gpu_nms(dets, thresh):
     return list(order[keep])
 
 
+def cpu_nms(dets, thresh):
+    """cpu_nms.pyx:17-68: float32 boxes, areas and overlap; box j is suppressed by an earlier kept box i when
+    `ovr >= thresh`, where `thresh` is the pyx's C DOUBLE (`np.float thresh`) and `ovr` a float32 promoted to it.  So an
+    overlap of exactly float32(0.7) = 0.699999988 does NOT reach a threshold of 0.7, while exactly float32(0.3) = 0.300000012
+    does reach 0.3.  Returns the kept indices into `dets` in scan order."""
+    dets = np.asarray(dets, dtype=F32)
+    n = dets.shape[0]
+    if n == 0:
+        return []
+    order = argsort_desc(dets[:, 4])
+    b = dets[order, :4]
+    suppressed = np.zeros(n, dtype=bool)
+    keep = []
+    t = float(thresh)
+    for i in range(n):
+        if suppressed[i]:
+            continue
+        keep.append(int(order[i]))
+        if i + 1 < n:
+            ov = iou_f32(b[i], b[i + 1:]).astype(np.float64)
+            suppressed[i + 1:] |= ov >= t
+    return keep
+
+
 def py_nms(dets, thresh):
     """nms.py:45-82, arithmetic in the dtype of `dets`."""
     dets = np.asarray(dets)
@@ -92,12 +122,16 @@ def py_nms(dets, thresh):
     return keep
 
 
-def soft_nms(dets, thresh, max_dets=-1):
+def soft_nms(dets, thresh, max_dets=-1, return_index=False):
     """Gaussian soft-NMS, nms.py:96-141 with `rescore` :85-93
-    (score *= exp(-ovr^2 / thresh)); returns the re-scored rows in pick order."""
+    (score *= exp(-ovr^2 / thresh)); returns the re-scored rows in pick order (return_index: and the picked row indices).
+    Every pick is the maximum of the CURRENT scores; among exactly equal ones the largest original index (the module
+    docstring's rule).  The reference re-sorts the previous order with its unstable `argsort()[::-1]`, which leaves the
+    order of equals open; a stable re-sort of the previous ORDER would make the tie order depend on the pick history
+    (four disjoint boxes at 0.5 would come out 3, 0, 2, 1), so the re-sort here is by (score, original index)."""
     dets = np.array(dets, copy=True)
     if dets.shape[0] == 0:
-        return np.zeros((0, 5))
+        return (np.zeros((0, 5)), np.zeros(0, dtype=np.intp)) if return_index else np.zeros((0, 5))
     x1, y1, x2, y2 = (dets[:, i] for i in range(4))
     scores = dets[:, 4]
     areas = (x2 - x1 + 1) * (y2 - y1 + 1)
@@ -115,8 +149,9 @@ def soft_nms(dets, thresh, max_dets=-1):
         inter = w * h
         ovr = inter / (areas[i] + areas[r] - inter)
         scores = scores[1:] * np.exp(-ovr ** 2 / thresh)
-        tmp = argsort_desc(scores)
+        tmp = np.lexsort((r, scores))[::-1]          # score descending, equal scores: larger original index first
         order = r[tmp]
         scores = scores[tmp]
         keep.append(i)
-    return dets[np.asarray(keep, dtype=np.intp), :]
+    keep = np.asarray(keep, dtype=np.intp)
+    return (dets[keep, :], keep) if return_index else dets[keep, :]

@@ -40,11 +40,17 @@ def detections(scores, boxes, num_classes=81, thresh=1e-3, nms_param=0.6, soft=T
         else:
             keep = py_nms(cls_dets, nms_param)
             all_boxes[j] = cls_dets[keep, :] if len(keep) else np.zeros((0, 5))
-    if max_per_image > 0:
-        image_scores = np.hstack([all_boxes[j][:, -1] for j in range(1, num_classes)])
-        if len(image_scores) > max_per_image:
-            image_thresh = np.sort(image_scores)[-max_per_image]
-            for j in range(1, num_classes):
-                keep = np.where(all_boxes[j][:, -1] >= image_thresh)[0]
-                all_boxes[j] = all_boxes[j][keep, :]
-    return all_boxes[1:]
+    return image_cut(all_boxes[1:], max_per_image)[0]
+
+
+def image_cut(per_class, max_per_image=100):
+    """tester.py:270-277 on the per-class lists ([k,5] arrays, classes 1..C-1): when the image has more than max_per_image
+    detections, keep those whose score is >= the max_per_image-th largest -- EVERY detection tied with it survives, so more
+    than max_per_image can.  -> (lists after the cut, image threshold or -inf, number of detections before the cut)."""
+    per_class = list(per_class)
+    image_scores = np.hstack([d[:, -1] for d in per_class]) if per_class else np.zeros(0)
+    thresh = -np.inf
+    if max_per_image > 0 and len(image_scores) > max_per_image:
+        thresh = np.sort(image_scores)[-max_per_image]
+        per_class = [d[np.where(d[:, -1] >= thresh)[0], :] for d in per_class]
+    return per_class, thresh, len(image_scores)

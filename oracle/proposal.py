@@ -61,8 +61,10 @@ def proposal(cls_prob, bbox_deltas, im_info, feat_stride=16, scales=(4, 8, 16, 3
     props = props[order]
     scores = scores[order]
     det = np.hstack((props, scores)).astype(F32)
-    # gpu_nms re-sorts by score (gpu_nms.pyx:28); `det` is already descending and
-    # tie-free, so the scan order is the row order.
+    # gpu_nms re-sorts by score (gpu_nms.pyx:28); `det` is already descending, so the
+    # scan order is the row order.  Among exactly tied scores that row order is the
+    # project's rule applied ONCE, to the original anchor index (argsort_desc above:
+    # larger index first); the re-sort of the sorted list is taken as the identity.
     keep = nms_sorted_f32(det[:, :4], threshold)
     n_kept = len(keep)
     if post_nms_top_n > 0:

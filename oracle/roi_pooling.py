@@ -18,6 +18,27 @@ def _round_half_away(x):
     return int(np.floor(x + F32(0.5))) if x >= 0 else int(np.ceil(x - F32(0.5)))
 
 
+def roi_windows(roi, H, W, pooled_size=(7, 7), spatial_scale=0.0625):
+    """Pooling windows of one roi (batch_idx, x1, y1, x2, y2): -> (hs, he) [PH], (ws, we) [PW] int arrays, clamped to the
+    map; bin (ph, pw) covers rows hs[ph]:he[ph] and columns ws[pw]:we[pw] (empty when he <= hs or we <= ws)."""
+    PH, PW = pooled_size
+    s = F32(spatial_scale)
+    roi = np.asarray(roi, dtype=F32)
+    rs_w = _round_half_away(roi[1] * s)
+    rs_h = _round_half_away(roi[2] * s)
+    re_w = _round_half_away(roi[3] * s)
+    re_h = _round_half_away(roi[4] * s)
+    rw = max(re_w - rs_w + 1, 1)
+    rh = max(re_h - rs_h + 1, 1)
+    bin_h = F32(rh) / F32(PH)
+    bin_w = F32(rw) / F32(PW)
+    hs = np.array([min(max(int(np.floor(F32(ph) * bin_h)) + rs_h, 0), H) for ph in range(PH)])
+    he = np.array([min(max(int(np.ceil(F32(ph + 1) * bin_h)) + rs_h, 0), H) for ph in range(PH)])
+    ws = np.array([min(max(int(np.floor(F32(pw) * bin_w)) + rs_w, 0), W) for pw in range(PW)])
+    we = np.array([min(max(int(np.ceil(F32(pw + 1) * bin_w)) + rs_w, 0), W) for pw in range(PW)])
+    return (hs, he), (ws, we)
+
+
 def roi_pooling(data, rois, pooled_size=(7, 7), spatial_scale=0.0625, return_argmax=False):
     """data [B, C, H, W] fp32, rois [R, 5] (batch_idx, x1, y1, x2, y2) fp32
     -> out [R, C, PH, PW] fp32 (argmax = flat h*W+w index or -1)."""

@@ -3,7 +3,7 @@
 | reference                                   | here                                                                    |
 |---------------------------------------------|-------------------------------------------------------------------------|
 | `gpu_nms(dets f32[n,5], thresh, device_id)` | sort on the host exactly like the .pyx, then the C symbol `_nms` (`lib/nms/gpu_nms.hpp:1-2`, same prototype, host pointers) |
-| `cpu_nms(dets, thresh)`                     | same kernels; float32 IoU, suppress when `ovr >= thresh` (cpu_nms.pyx:65) = `ovr > nextafter(thresh, -inf)` |
+| `cpu_nms(dets, thresh)`                     | same kernels; float32 IoU, suppress when `ovr >= thresh` with `thresh` a C double (cpu_nms.pyx:17,65) = `ovr > pred(t)`, t the smallest float32 >= thresh |
 | `nms(dets, thresh)` (numpy, dets' dtype)    | `relnet_class_nms_ex` greedy branch, float64, keeps `ovr <= thresh` (nms.py:79) |
 | `soft_nms(dets, thresh, max_dets)`          | `relnet_class_nms_ex` Gaussian branch, float64 (nms.py:85-141)          |
 | `*_wrapper(thresh[, ...])`                  | the same closures (nms.py:21-42)                                        |
@@ -11,7 +11,9 @@
 Return conventions are the reference's: `gpu_nms` / `cpu_nms` / `nms` return the kept indices into the UNSORTED input
 (in descending score order), `soft_nms` returns the re-scored `dets[keep]` rows and, like the reference (nms.py:114),
 writes the decayed scores back into the caller's array.  Ties: the reference's `argsort()[::-1]` is an unstable
-sort; here equal scores are ordered by descending index.  There is no CPU fallback: without a GPU these raise.
+sort; here, as everywhere in the project (DESIGN.md "Tolerances"; oracle/nms.py states the same rule), equal scores are
+ordered by descending index -- in `soft_nms` at EVERY pick: the maximum of the current scores, and among exactly equal ones
+the largest original index.  There is no CPU fallback: without a GPU these raise.
 """
 import ctypes
 
@@ -54,7 +56,10 @@ def cpu_nms(dets, thresh):
     if dets.shape[0] == 0:
         return []
     sorted_dets, order = _sorted_f32(dets)
-    t = np.nextafter(np.float32(thresh), np.float32(-np.inf))                # ovr >= t  <=>  ovr > pred(t) in float32
+    t = np.float32(thresh)
+    if float(t) < float(thresh):                                             # the pyx compares the float32 overlap with a DOUBLE thresh:
+        t = np.nextafter(t, np.float32(np.inf))                              # ovr >= thresh  <=>  ovr >= t, t the smallest float32 >= thresh
+    t = np.nextafter(t, np.float32(-np.inf))                                 # ovr >= t  <=>  ovr > pred(t) in float32
     return [int(i) for i in order[_nms_c(sorted_dets, float(t), 0)]]
 
 
