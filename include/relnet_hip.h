@@ -724,6 +724,43 @@ int relnet_recall_match(const float* boxes, long box_bs, long box_rs, const floa
                         unsigned long long* hits, unsigned long long* num_pos, unsigned long long* area_count, int* n_cand,
                         int* added, double* overlaps, int B, int P, int n_images, int A, int T, int gt_cap, void* stream);
 
+/* ---- Training metrics (csrc/metrics.hip), the device twin of metric.py = relation_rcnn/core/metric.py ---------------------------
+ * Every entry takes device pointers and a stream, allocates nothing, never synchronises and ADDS into slots of a caller-owned
+ * accumulator, so it can be captured into a hipGraph and counts on every replay.  Integer slots are int64 (one integer atomic
+ * per workgroup); float sums are double and bitwise reproducible for the same inputs: no floating-point atomic, per-workgroup
+ * partials in `workspace`, added in workgroup order by the workgroup that arrives last.  workspace:
+ * relnet_metric_workspace_bytes() bytes, 8-byte aligned, zeroed ONCE when it is created (the kernels leave it zeroed); launches
+ * that share one must be ordered by their stream.  Resetting the accumulator is a hipMemsetAsync of it.
+ * A double slot is updated by a plain read-modify-write of ONE workgroup, not by an atomic: two launches that may run concurrently
+ * (different streams, parallel branches of a graph) must never be given the SAME slot.  Distinct slots of one accumulator are fine,
+ * also inside one cache line.  This is a hard contract of the entries; metric.TrainMetrics keeps it by writing the RPN slots only from
+ * the trainer's side stream and every other slot only from its main stream.
+ * The accumulator of metric.TrainMetrics, 16 int64 then 8 double (192 bytes):
+ *   counts  0 RPNAcc sum         1 RPNAcc / RPNLogLoss num_inst     2 RPNL1Loss num_inst
+ *           3 RCNNAcc sum        4 RCNNAcc / RCNNLogLoss num_inst   5 RCNNL1Loss num_inst
+ *           6 NMSLoss_pos / _neg num_inst (images: one image = one executor in the reference)
+ *           7 NMSAcc_pos sum     8 NMSAcc_pos num_inst    9 NMSAcc_neg sum    10 NMSAcc_neg num_inst     11..15 unused
+ *   sums    0 RPNLogLoss   1 RPNL1Loss   2 RCNNLogLoss   3 RCNNL1Loss   4 NMSLoss_pos   5 NMSLoss_neg   6, 7 unused
+ * relnet_metric_softmax: prob [outer, C, inner] (what relnet_softmax_output_ex writes), label [outer * inner] float; a position
+ *   is kept iff (int)label != -1 (metric.py: .astype('int32')).  *correct += #(argmax_c prob == label), *inst += #kept,
+ *   *logloss += sum of -log((double)(float)(p[label] + 1e-14f)).  argmax = the lowest class among equal maxima, a NaN counts as
+ *   the maximum (numpy argmax, metric.py:75; for the RPN the reference calls mx.ndarray.argmax_channel, an MXNet primitive that
+ *   is not in the reference tree: the first-maximum rule there is this project's restatement, not a pin).  A kept label outside
+ *   [0, C) is outside the contract: nothing is read for it, its term is -log(1e-14f).  Loads: inner == 1 one wavefront per row; C == 2
+ *   (the RPN) 16-byte loads when inner % 4 == 0, 8-byte loads when inner % 2 == 0 (9 anchors on an odd-sized map), each with operands
+ *   aligned to the load, otherwise one position per thread; the result does not depend on which of them ran beyond the order of the sum.
+ * relnet_metric_sum_count: *sum += sum(x [n]); with x2 [n] also *sum2 += sum(x2); *count += #(label [n_label] != -1) (a float
+ *   compare, metric.py:154) + inst_inc.  x2, label, count may be null (label null <=> n_label 0).
+ * relnet_metric_nms_acc: target, cond [n]; counts[0] += #(target > 0.5 and cond > 0.5), counts[1] += #(target > 0.5),
+ *   counts[2] += #(target < 0.5 and cond < 0.5), counts[3] += #(target < 0.5): strict compares in float32, an element equal
+ *   to 0.5 is on neither side (metric.py:236-248). */
+long relnet_metric_workspace_bytes(void);
+int relnet_metric_softmax(const float* prob, const float* label, long outer, int C, long inner, long long* correct,
+                          long long* inst, double* logloss, void* workspace, void* stream);
+int relnet_metric_sum_count(const float* x, const float* x2, long n, const float* label, long n_label, long inst_inc,
+                            double* sum, double* sum2, long long* count, void* workspace, void* stream);
+int relnet_metric_nms_acc(const float* target, const float* cond, long n, long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,10 @@ _SIGNATURES = {
     'relnet_coco_accumulate_workspace_bytes': (C.c_long, [_l, _i, _i]),
     'relnet_coco_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _l] + [_i] * 6 + [_vp]),
     'relnet_recall_match': (C.c_int, [_vp, _l, _l, _vp, _vp, _vp, _f] + [_vp] * 12 + [_i] * 6 + [_vp]),
+    'relnet_metric_workspace_bytes': (C.c_long, []),
+    'relnet_metric_softmax': (C.c_int, [_vp, _vp, _l, _i, _l, _vp, _vp, _vp, _vp, _vp]),
+    'relnet_metric_sum_count': (C.c_int, [_vp, _vp, _l, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp]),
+    'relnet_metric_nms_acc': (C.c_int, [_vp, _vp, _l, _vp, _vp]),
 }
 
 

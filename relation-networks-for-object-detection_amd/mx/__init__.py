@@ -16,6 +16,8 @@ import types
 from . import registry as _R
 from . import graph as _S
 from . import ndarray as nd
+from . import ndarray  # noqa: F401  (mx.ndarray.argmax_channel)
+from . import metric, lr_scheduler  # noqa: F401
 from .ndarray import Context, cpu, gpu, NDArray  # noqa: F401
 from .graph import Symbol  # noqa: F401
 
@@ -99,6 +101,8 @@ def install(py2_shims=True):
     sys.modules['mxnet'] = me
     sys.modules['mxnet.symbol'] = sym
     sys.modules['mxnet.ndarray'] = nd
+    sys.modules['mxnet.metric'] = metric
+    sys.modules['mxnet.lr_scheduler'] = lr_scheduler        # (`from mxnet.lr_scheduler import LRScheduler`)
     pkg = importlib.import_module(__name__.rsplit('.', 1)[0])
     op = importlib.import_module(pkg.__name__ + '.operator_py')
     sys.modules.setdefault('operator_py', op)

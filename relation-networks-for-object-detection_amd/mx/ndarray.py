@@ -109,6 +109,13 @@ def array(source, ctx=None, dtype=None):
     return NDArray(torch.as_tensor(a).to(_dev(ctx)))
 
 
+def argmax_channel(data):
+    """Index of the maximum over axis 1, as float32 (mx.nd.argmax_channel; the host metrics' only user).  The FIRST of equal
+    maxima, numpy's rule: MXNet's own kernel is not in the reference tree, so this is a restatement, not a pin."""
+    a = data.asnumpy() if isinstance(data, NDArray) else np.asarray(data)
+    return NDArray(torch.as_tensor(np.argmax(a, axis=1).astype(np.float32)))
+
+
 def zeros(shape, ctx=None, dtype=None, **kw):
     return NDArray(torch.zeros(tuple(shape) if not isinstance(shape, int) else (shape,), device=_dev(ctx)))
 

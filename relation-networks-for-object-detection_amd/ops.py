@@ -573,6 +573,59 @@ def recall_match(boxes, image_pos, gt_off, gt_box, gt_mask, thresholds, area_rng
 
 
 # ---------------------------------------------------------------------------------------
+# Training metrics (csrc/metrics.hip; the host definition is metric.py)
+# ---------------------------------------------------------------------------------------
+def metric_workspace(device):
+    """Fold workspace of the metric kernels: zeroed here, once; the kernels leave it zeroed.  One per stream that launches them."""
+    return torch.zeros(_lib.load().relnet_metric_workspace_bytes() // 8, device=device, dtype=torch.int64)
+
+
+def _slot(t, i, dtype):
+    assert t.dtype == dtype and t.is_contiguous() and 0 <= i < t.numel()
+    return t.data_ptr() + 8 * i
+
+
+def metric_softmax(prob, label, counts, sums, correct_slot, inst_slot, logloss_slot, workspace):
+    """prob [outer, C] or [outer, C, ...] float32 (softmax over axis 1), label float class ids (-1: ignored), one per position.
+    counts[correct_slot] += #(argmax == label), counts[inst_slot] += #(label != -1), sums[logloss_slot] += sum of
+    -log(p[label] + 1e-14).  counts int64, sums float64 (the accumulator of metric.TrainMetrics).  No host synchronisation."""
+    _chk(prob, label, counts, sums, workspace)
+    assert prob.dtype == torch.float32 and prob.is_contiguous() and prob.dim() >= 2
+    outer, Cn = prob.shape[0], prob.shape[1]
+    inner = prob[0, 0].numel()
+    if label.dtype != torch.float32 or not label.is_contiguous():
+        label = label.to(torch.float32).contiguous()
+    if label.numel() != outer * inner:
+        raise ValueError("metric_softmax: label has %d entries, expected %d" % (label.numel(), outer * inner))
+    _lib.call('relnet_metric_softmax', prob.data_ptr(), label.data_ptr(), outer, Cn, inner, _slot(counts, correct_slot, torch.int64),
+              _slot(counts, inst_slot, torch.int64), _slot(sums, logloss_slot, torch.float64), workspace.data_ptr(), _stream())
+
+
+def metric_sum_count(x, counts, sums, sum_slot, workspace, label=None, count_slot=None, inst_inc=0, x2=None, sum2_slot=None):
+    """sums[sum_slot] += sum(x) (float32 tensor, summed in float64); with x2 also sums[sum2_slot] += sum(x2);
+    counts[count_slot] += #(label != -1) + inst_inc."""
+    _chk(x, x2, label, counts, sums, workspace)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    if x2 is not None:
+        assert x2.dtype == torch.float32 and x2.is_contiguous() and x2.numel() == x.numel() and sum2_slot is not None
+    if label is not None and (label.dtype != torch.float32 or not label.is_contiguous()):
+        label = label.to(torch.float32).contiguous()
+    assert count_slot is not None or (label is None and not inst_inc)
+    _lib.call('relnet_metric_sum_count', x.data_ptr(), _ptr(x2), x.numel(), _ptr(label), 0 if label is None else label.numel(), int(inst_inc),
+              _slot(sums, sum_slot, torch.float64), 0 if x2 is None else _slot(sums, sum2_slot, torch.float64),
+              0 if count_slot is None else _slot(counts, count_slot, torch.int64), workspace.data_ptr(), _stream())
+
+
+def metric_nms_acc(target, cond, counts, first_slot):
+    """counts[first_slot .. first_slot + 3] += #(target > 0.5 and cond > 0.5), #(target > 0.5), #(target < 0.5 and cond < 0.5),
+    #(target < 0.5)."""
+    _chk(target, cond, counts)
+    assert target.dtype == cond.dtype == torch.float32 and target.is_contiguous() and cond.is_contiguous() and target.numel() == cond.numel()
+    assert first_slot + 4 <= counts.numel()
+    _lib.call('relnet_metric_nms_acc', target.data_ptr(), cond.data_ptr(), target.numel(), _slot(counts, first_slot, torch.int64), _stream())
+
+
+# ---------------------------------------------------------------------------------------
 # NHWC convolution (implicit GEMM on the bf16 MFMA kernel)
 # ---------------------------------------------------------------------------------------
 def pack_conv_weight(w_oihw, dtype=torch.bfloat16, device='cuda'):

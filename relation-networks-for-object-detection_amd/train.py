@@ -98,7 +98,11 @@ class _Flat(object):
 
 
 class Trainer(object):
-    def __init__(self, params, cfg=None, device='cuda', im_hw=(600, 1000)):
+    def __init__(self, params, cfg=None, device='cuda', im_hw=(600, 1000), metrics=None):
+        """metrics: a metric.TrainMetrics (default None: no metric launch, no extra output).  With one, every step adds the reference's
+        training metrics into its device accumulator -- no host synchronisation, also inside a CapturedStep -- and `out` additionally carries
+        rpn_cls_prob, rpn_label, cls_prob, nms_conditional_score and the loss tensors behind the loss scalars (rpn_bbox_loss_map, bbox_loss_map,
+        nms_pos_loss_map, nms_neg_loss_map): the output list of the reference's train graph, which metric.py's host classes take."""
         self.cfg = cfg or TrainConfig()
         check_pooling(self.cfg)
         self.device, self.im_hw = device, im_hw
@@ -209,6 +213,9 @@ class Trainer(object):
         self.anchors_host = generate_anchors(c.feat_stride, c.anchor_ratios, c.anchor_scales)      # float64 [A,4], host (kernel argument)
         self.anchors = torch.as_tensor(self.anchors_host, dtype=torch.float64, device=dev)
         self.step_count = 0
+        self.metrics = metrics
+        if metrics is not None:         # which metrics exist follows the graph: RPN ones with an RPN in it, NMS ones with the learn-NMS head
+            metrics.has_rpn, metrics.has_nms = not self.fpn, bool(c.learn_nms)
         # state that used to be created on first use -- inside a hipGraph capture that turned into a captured fill / mid-capture
         # stream and attribute calls: the device step counter of the anchor sampler, the RPN side stream, the queues of
         # the deferred gradient work -- weight-gradient products and bias-gradient column sums, each launched grouped when a gradient
@@ -441,8 +448,8 @@ class Trainer(object):
             # -- RPN losses (per image, like one image per device in the reference)
             score_nchw = rpn[..., :na2].permute(0, 3, 1, 2).contiguous()                                 # [B,2A,h,w]
             # per-image 'valid' normalisation (one image per executor in the reference) in ONE launch: group = one image's anchors
-            _, d_score = losses.softmax_output(score_nchw.view(B, 2, -1), lbl, multi_output=True, use_ignore=True,
-                                               ignore_label=-1.0, group=(na2 // 2) * h * wd_)
+            rpn_prob, d_score = losses.softmax_output(score_nchw.view(B, 2, -1), lbl, multi_output=True, use_ignore=True,
+                                                      ignore_label=-1.0, group=(na2 // 2) * h * wd_)
             d_score = d_score.view(B, na2, h, wd_)
             delta = rpn[..., na2:].contiguous()                                                          # NHWC [B,h,w,4A]
             tgt = tgt_in.permute(0, 2, 3, 1).contiguous()
@@ -462,6 +469,12 @@ class Trainer(object):
                 br['ev'] = torch.cuda.Event()
                 br['ev'].record()               # main resumes here (rois and their targets exist); the RPN head's backward follows on this stream
                 br['bwd'] = (conv4, r, d_rpn)   # ... once the main stream has made the weight copies it reads (enqueued below)
+            if self.metrics is not None:
+                # RPNAcc / RPNLogLoss / RPNL1Loss on this stream, BEHIND the event the main stream resumes at: they never lengthen the path to
+                # ROI pooling (one image per step: this branch is the longer one), only the RPN head's backward starts two small launches later
+                self.metrics.add_rpn(rpn_prob, lbl, rpn_l1)
+                br.update(rpn_cls_prob=rpn_prob, rpn_label=lbl, rpn_bbox_loss_map=rpn_l1)
+                out['rpn_cls_prob'], out['rpn_label'], out['rpn_bbox_loss_map'] = rpn_prob, lbl, rpn_l1
 
         def rpn_backward(conv4, r, d_rpn):
             # RPN head backward (joins the trunk at conv4), on the side stream beside ROI pooling / the 2FC head / the learn-NMS branch (launches of
@@ -678,11 +691,14 @@ class Trainer(object):
         else:       # ENABLE_OHEM false (symbols/..._learn_nms_1024_...:232-241): every roi counts (padding rows of a short proposal list keep label -1
             labels_ohem, weights_ohem = label, bbox_weight          # and are ignored), the box loss is scaled by 1 / 300 (BATCH_ROIS < 0)
             box_norm = 300
-        _, d_cls = losses.softmax_output(cls_score.view(B * R, -1), labels_ohem.reshape(-1), use_ignore=True, ignore_label=-1.0, group=R)
+        cls_prob, d_cls = losses.softmax_output(cls_score.view(B * R, -1), labels_ohem.reshape(-1), use_ignore=True, ignore_label=-1.0, group=R)
         d_cls = d_cls.view(B, R, -1)
         l1, d_bbox = losses.smooth_l1_loss(bbox_pred, bbox_target, weights_ohem, 1.0, 1.0 / box_norm)
         out['bbox_loss'] = T.scalar_sum(l1, 1.0 / B)
         out['num_ohem'] = T.scalar_sum(labels_ohem, count_nonneg=True)
+        if self.metrics is not None:        # RCNNAcc / RCNNLogLoss / RCNNL1Loss (padding rows of a short proposal list have label -1: not counted)
+            self.metrics.add_rcnn(cls_prob, labels_ohem.reshape(-1), l1)
+            out['cls_prob'], out['bbox_loss_map'] = cls_prob.view(B, R, -1), l1
         d_x2_lnms = None
         if c.learn_nms:     # the learn-NMS head sees the first N (non-gt) rows; its gradient joins cls_score and fc_all_2_relu
             d_cls_l, d_x2_lnms, lo = self._lnms_forward_backward(cls_score[:, :N], bbox_pred[:, :N], rois_t[:, :N].contiguous(),
@@ -799,6 +815,9 @@ class Trainer(object):
         pos, neg, d_multi = losses.nms_loss(multi, target, F, Tn, c.nms_loss_scale, c.nms_pos_scale, c.nms_eps)
         lo = dict(nms_pos_loss=T.scalar_sum(pos, 1.0 / B), nms_neg_loss=T.scalar_sum(neg, 1.0 / B), nms_multi_score=multi, nms_multi_target=target,
                   sorted_score=sorted_score, nms_rank_idx=rank_idx, nms_class_boxes=class_boxes)
+        if self.metrics is not None:        # NMSLoss_pos / _neg (B images: one image = one executor in the reference), NMSAcc_pos / _neg
+            self.metrics.add_nms(target, cond, pos, neg, B)
+            lo.update(nms_conditional_score=cond, nms_pos_loss_map=pos, nms_neg_loss_map=neg)
         # ---------------- adjoint ----------------
         if fused:
             d_sorted = torch.empty((B, F, C), device=dev, dtype=torch.float32)
@@ -1226,10 +1245,10 @@ class FPNTrainer(Trainer):
 
     scales = (1 / 4.0, 1 / 8.0, 1 / 16.0, 1 / 32.0)
 
-    def __init__(self, params, cfg=None, device='cuda'):
+    def __init__(self, params, cfg=None, device='cuda', metrics=None):
         cfg = cfg or TrainConfig()
         cfg.fpn = True
-        Trainer.__init__(self, params, cfg, device, im_hw=None)
+        Trainer.__init__(self, params, cfg, device, im_hw=None, metrics=metrics)
 
     def _forward_backward_impl(self, data, im_info, gt_boxes, proposals, num_gt=None, num_proposals=None):
         """data [B,3,H,W] (H, W multiples of 32), proposals [B,N,4] fp32, gt_boxes [B,G,5]; num_proposals [B] int32
