@@ -251,12 +251,24 @@ int relnet_bottleneck_chain(const void* mid2, const void* x, const void* w3f, co
  * relnet_bottleneck_chain (or NULL).  mid = 64; w3f / wpf = relnet_pack_w_frag images of W3 / Wp [256][64]; x_in [P][64] dense bf16. */
 int relnet_bottleneck_chain_proj(const void* mid2, const void* x_in, const void* w3f, const void* wpf, const void* w1f,
                                  const float* b3p, const float* b1, void* x_next, void* mid1_next, long P, int mid, void* stream);
+/* Last unit of a stage whose successor subsamples by two (res2c / res3b3 of the non-FPN trunk: only res3a / res4a's stride-2 1x1
+ * layers read the unit's output): x_next = relu(W3 . mid2 + b3 + x) at the even (y, x) pixels only.  mid2 [B][Ho][Wo][mid] and x_next
+ * [B][Ho][Wo][4 mid] are compact maps, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1; the shortcut x [B][H][W][4 mid] is the full map and is
+ * read at (2 yo, 2 xo).  Dense NHWC bf16; x_next must not alias x.  mid = 64 or 128; w3f as in relnet_bottleneck_chain, whose x_next it
+ * equals bit for bit at those pixels.  The FULL 4 mid-channel map must stay below 4 GiB (32-bit byte offsets).              */
+int relnet_bottleneck_chain_s2(const void* mid2, const void* x, const void* w3f, const float* b3, void* x_next, int B, int H,
+                               int W, int mid, void* stream);
 
 /* 3x3 / stride 1 / pad 1 convolution + bias (+ ReLU) of a dense 64-channel NHWC bf16 tensor with the input tile and its halo
  * resident in LDS (res2*_branch2b + BN + ReLU, resnet_v1_101_rcnn_base.py:52-56): the input is fetched 1.33 x instead of once
  * per tap.  w_frag = relnet_pack_w_frag of the packed weight [64][576] (k = (r * 3 + s) * 64 + c).                        */
 int relnet_conv3x3_c64(const void* in, const void* w_frag, const float* bias, int relu, void* out, int B, int H, int W,
                        void* stream);
+/* The same convolution at stride 2 (the 3x3 layer of a unit that relnet_bottleneck_chain_s2 ends): in [B][H][W][64] -> out
+ * [B][Ho][Wo][64], Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, out[b][yo][xo] = relnet_conv3x3_c64's result at (2 yo, 2 xo) bit for bit
+ * (same k-steps in the same order; 4 x 32 output pixels per workgroup, halo rows stored with even and odd columns apart). */
+int relnet_conv3x3_c64_s2(const void* in, const void* w_frag, const float* bias, int relu, void* out, int B, int H, int W,
+                          void* stream);
 
 
 /* Row-panel form of the 1x1 convolutions (csrc/gemm.hip:gemm_panelw_kernel): `w_frag` is the weight matrix re-ordered once

@@ -142,6 +142,8 @@ class Backbone(object):
             self.stage_split = {int(a): int(b) for a, b in (kv.split(':') for kv in env.split(','))}
         if os.environ.get('RELNET_INPLACE_EXPAND') is not None:
             self.inplace_expand = os.environ['RELNET_INPLACE_EXPAND'] not in ('', '0')
+        if os.environ.get('RELNET_QUARTER_UNITS') is not None:
+            self.quarter_units = os.environ['RELNET_QUARTER_UNITS'] not in ('', '0')
         self.impl = impl or ('hip' if dtype == torch.bfloat16 else ('hip32' if dtype == torch.float32 and torch.device(device).type == 'cuda' else 'miopen'))
         if self.impl == 'hip' and torch.device(device).type == 'cuda':
             ops.asm_selfcheck()          # tile 19 (AGPR accumulators across asm statements) against the compiler-scheduled tile, once per process
@@ -278,6 +280,8 @@ class Backbone(object):
         y_next = None
         side, hooked = None, None
         self.last_chain_units, self.last_side_stream, self.last_stage_split = [], False, {}      # what actually ran (reported by oracle/parity.py)
+        self.last_quarter_units = []
+        compact = False                   # x is the even-pixel quarter of the previous stage's output (its last unit ran in the quarter form)
         ui = 0
         while ui < len(self.units):
             unit = self.units[ui]
@@ -301,7 +305,9 @@ class Backbone(object):
                 x = self._run_stage_split(x, stage_units, nsplit)
                 ui += len(stage_units)
                 continue
-            x, y_next = self._unit_hip(x, unit, y_next, inplace=self.inplace_expand)
+            quarter = self._quarter_ok(x, unit, self.units[ui + 1] if ui + 1 < len(self.units) else None)
+            x, y_next = self._unit_hip(x, unit, y_next, inplace=self.inplace_expand, quarter=quarter, subsampled=compact)
+            compact = quarter
             ui += 1
         conv5 = x
         nchw = lambda t: t.permute(0, 3, 1, 2)
@@ -333,6 +339,29 @@ class Backbone(object):
     #: convolution has read it).  Halves the activation footprint of a stage; RELNET_INPLACE_EXPAND=0 for the A/B.
     inplace_expand = True
 
+    #: the last unit of res2 / res3 computed at the even (y, x) pixels only (non-FPN graphs): nothing but the stride-2 1x1 layers of
+    #: res3a / res4a reads its output, so its 3x3 layer runs at stride 2 and its expand kernel gathers the shortcut
+    #: (ops.conv3x3_halo_s2 / conv2d_nhwc(stride=2), ops.bottleneck_chain_s2); the next unit then runs at stride 1 on the compact map.
+    #: Same bits as the dense form at the pixels that are read.  RELNET_QUARTER_UNITS=0 for the A/B.
+    quarter_units = True
+
+    def _quarter_ok(self, x, unit, nxt):
+        """Does `unit` (about to run on x) run in the quarter form?  Its successor must be a stride-2 projection unit of the next stage and
+        the only reader of its output (no FPN laterals), neither stage may be split, and the gather kernel must be worthwhile at the
+        COMPACT pixel count."""
+        stage, nm, ic, mc, oc, stride, dil, proj = unit
+        if not self.quarter_units or self.fpn or nxt is None or nxt[0] != stage + 1 or nxt[5] != 2 or not nxt[7]:
+            return False
+        ch = self.chain.get(nm)
+        if ch is None or ch[1] is not None or mc not in ops.CHAIN_S2_MIDS or proj or dil != 1 or (self.dcn and stage == 5):
+            return False
+        if mc in ops.HALO3_CHANNELS and ('res%s_branch2b' % nm) not in self.halo3:
+            return False
+        if self.stage_split and (self._stage_split(stage, x, unit) > 1 or self._stage_split(nxt[0], x, nxt) > 1):
+            return False
+        B, H, W, C = x.shape
+        return C == oc and x.numel() * 2 < (1 << 32) and ops.chain_worthwhile(B * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1), mc)
+
     def _stage_split(self, stage, x, unit):
         return int(self.stage_split.get(stage, 1)) if self.stage_split else 1
 
@@ -352,12 +381,28 @@ class Backbone(object):
                 out[lo:hi].copy_(xs)
         return out
 
-    def _unit_hip(self, x, unit, y_pre=None, sc_out=None, inplace=False, force_chain=False):
+    def _unit_hip(self, x, unit, y_pre=None, sc_out=None, inplace=False, force_chain=False, quarter=False, subsampled=False):
         """One bottleneck unit (resnet_v1_101_rcnn_base.py: branch1 | branch2a -> 2b -> 2c, + shortcut, ReLU) on the HIP kernels.
         y_pre: this unit's reduce output if the previous unit's chain kernel already produced it.  sc_out: where the projection
         shortcut of a first unit is written.  inplace: the expand kernel may write x_next over its shortcut operand.
+        quarter: only the even (y, x) pixels of x_next are produced, as a compact map (see `quarter_units`).  subsampled: x is such a
+        compact map, i.e. this unit's stride 2 has already been applied.
         -> (x_next, reduce output of the NEXT unit | None)"""
         stage, nm, ic, mc, oc, stride, dil, proj = unit
+        if subsampled:
+            assert stride == 2 and proj
+            stride = 1
+        if quarter:
+            y = y_pre if y_pre is not None else self._hconv(x, 'res%s_branch2a' % nm, relu=True)
+            if ('res%s_branch2b' % nm) in self.halo3:
+                y = ops.conv3x3_halo_s2(y.contiguous(), *self.halo3['res%s_branch2b' % nm], relu=True)
+            else:
+                y = self._hconv(y, 'res%s_branch2b' % nm, stride=2, pad=1, relu=True)
+            w3f, _, b3, _ = self.chain[nm]
+            if nm not in self.last_chain_units:
+                self.last_chain_units.append(nm)
+            self.last_quarter_units.append(nm)
+            return ops.bottleneck_chain_s2(y, x.contiguous(), w3f, b3), None
         fuse_proj = (nm in self.chain_proj and sc_out is None and x.is_contiguous()
                      and (force_chain or ops.chain_worthwhile(x.numel() // x.shape[-1], mc)))
         if fuse_proj:

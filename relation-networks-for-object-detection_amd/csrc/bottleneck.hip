@@ -47,6 +47,7 @@ struct ChainArgs {
   unsigned short* xn;         // [P][4 MID]
   unsigned short* m1;         // [P][MID]
   int P;
+  int H, W, Ho, Wo;           // GATHER: the full map x addresses and the compact one (Ho = (H - 1) / 2 + 1, Wo likewise); P = B * Ho * Wo
   int dbg;                    // timing ablations of chain256_roles_kernel (relnet_chain_debug; results are then WRONG): 1 = half of the weight
                               // loads, 2 = no weight loads, 4 = no shortcut-slice loads, 8 = no global stores
 };
@@ -66,13 +67,20 @@ struct ChainArgs {
 //  of all eight tiles, the mid-pass step only drains weight loads: 19.62 vs 19.59 ms per 54-image step, no gain; res5's expand is bound
 //  by its 2 MB weight stream per 256 pixels through the L2 -> LDS fill path)
 // MID = 256 with the second product (res4): chain256_roles_kernel below.
+// GATHER (expand-only, MID = 64 / 128; the last unit of res2 / res3, whose output only the stride-2 1x1 layers of the next stage read):
+//   mid2 and x_next are compact [B][Ho][Wo] maps of the even (y, x) pixels, the shortcut x stays the full [B][H][W] map and compact
+//   pixel q = (b, yo, xo) reads it at (b H + 2 yo) W + 2 xo.  The four row offsets of a lane (rows 8 i + drow of the tile) are worked
+//   out once per tile -- at the tile's last pass, for the tile after it -- and are the only per-lane address state (4 VGPRs, no
+//   scratch: a reload in the pass loop would put a vmcnt(0) between the prefetches).  Passes, k order, rounding points, LDS stage
+//   layout and stores are those of the dense form: the kept pixels carry the same bits.  Never in place (the shapes differ).
 // PROJ (MID = 64, resident weights; the first unit of res2, whose shortcut is a 1x1 projection of the unit's 64-channel input):
 //   x_next = relu(W3 . mid2 + Wp . x_in + (b3 + bp)) -- the projection is four more k-steps of the same accumulators instead of a
 //   separate convolution that writes a 4 MID-channel map (1.04 GB at 54 images) for this kernel to read back; no shortcut slice,
 //   one stage buffer per wave (written, then flushed in the same pass).  The shortcut is not rounded to bf16 on the way.
-template <int MID, bool STREAM, bool REDUCE = true, int KSPLIT = 1, bool PROJ = false>       // REDUCE = false: only x_next (no next reduce)
+template <int MID, bool STREAM, bool REDUCE = true, int KSPLIT = 1, bool PROJ = false, bool GATHER = false>       // REDUCE = false: only x_next (no next reduce)
 __global__ __launch_bounds__(512) void bottleneck_chain_kernel(ChainArgs a) {
   static_assert(!PROJ || (!STREAM && KSPLIT == 1), "the projection form exists for the resident-weight kernel");
+  static_assert(!GATHER || (!REDUCE && !PROJ && KSPLIT == 1), "the stride-2 gather exists for the plain expand-only forms");
   static_assert(KSPLIT == 1 || (STREAM && !REDUCE), "k-split passes exist for the streamed expand-only form");
   constexpr int COUT = 4 * MID, KS = MID / 16, KSS = KS / KSPLIT, RT = MID / 32, NP = COUT / 64;
   static_assert(!REDUCE || MID <= 128, "MID = 256 with the second product is chain256_roles_kernel");
@@ -103,7 +111,20 @@ __global__ __launch_bounds__(512) void bottleneck_chain_kernel(ChainArgs a) {
   __syncthreads();
   const int ntile = (a.P + 31) / 32;
   const int drow = lane >> 3, dslot = lane & 7;                // DMA / coalesced-store role: row 8 i + drow, chunk slot dslot
-  // shortcut slice of (tile base pixel p0, pass p) into stage buffer p & 1
+  // GATHER: byte offsets into x of the pixels that rows 8 i + drow of the tile at p0 read (clamped like the dense rows)
+  unsigned xrow[GATHER ? 4 : 1];
+  auto gather_rows = [&](int p0) {
+    if constexpr (GATHER) {
+      const unsigned hw = (unsigned)(a.Ho * a.Wo);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const unsigned q = (unsigned)min(p0 + 8 * i + drow, a.P - 1);
+        const unsigned b = q / hw, r = q - b * hw, yo = r / (unsigned)a.Wo, xo = r - yo * (unsigned)a.Wo;
+        xrow[i] = ((b * (unsigned)a.H + 2u * yo) * (unsigned)a.W + 2u * xo) * (COUT * 2u);
+      }
+    }
+  };
+  // shortcut slice of (tile base pixel p0, pass p) into stage buffer p & 1 (GATHER: of the tile gather_rows was last called for)
   auto issue_x = [&](int p0, int p) {
     if constexpr (PROJ) return;
     unsigned char* sb = stage + (p & 1) * 4096;
@@ -111,7 +132,8 @@ __global__ __launch_bounds__(512) void bottleneck_chain_kernel(ChainArgs a) {
     for (int i = 0; i < 4; ++i) {
       const int row = 8 * i + drow;
       // (32-bit byte offsets from the tensor base -- the host checks P * COUT * 2 < 2^32: half the address registers per row)
-      const unsigned off = ((unsigned)min(p0 + row, a.P - 1) * COUT + p * 64 + ((dslot ^ ((row >> 1) & 7)) << 3)) * 2u;
+      const unsigned off = GATHER ? xrow[i] + (p * 64 + ((dslot ^ ((row >> 1) & 7)) << 3)) * 2u
+                                  : ((unsigned)min(p0 + row, a.P - 1) * COUT + p * 64 + ((dslot ^ ((row >> 1) & 7)) << 3)) * 2u;
       __builtin_amdgcn_global_load_lds((gas_ptr)((const unsigned char*)a.x + off), (las_ptr)(sb + i * 1024), 16, 0, 0);
     }
   };
@@ -151,6 +173,7 @@ __global__ __launch_bounds__(512) void bottleneck_chain_kernel(ChainArgs a) {
   const int n_iter = STREAM ? ((ntile + 7) / 8 - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x
                             : (ntile - t_first + t_step - 1) / t_step;      // (streaming: idle waves of the last set still take part)
   if (n_iter <= 0) return;
+  gather_rows(t_first * 32);
   issue_x(t_first * 32, 0);
   issue_w(0);
   for (int it = 0; it < n_iter; ++it) {
@@ -180,7 +203,7 @@ __global__ __launch_bounds__(512) void bottleneck_chain_kernel(ChainArgs a) {
         if (kh == 0) {
           if (!PROJ && p > 0) flush(p0, p - 1);
           if (p + 1 < NP) issue_x(p0, p + 1);
-          else if (it + 1 < n_iter) issue_x(p0 + t_step * 32, 0);
+          else if (it + 1 < n_iter) { gather_rows(p0 + t_step * 32); issue_x(p0 + t_step * 32, 0); }
         }
         if (st + 1 < NP * KSPLIT) issue_w(st + 1);
         else if (it + 1 < n_iter) issue_w(0);
@@ -512,6 +535,7 @@ extern "C" int relnet_bottleneck_chain(const void* mid2, const void* x, const vo
   a.m2 = (const unsigned short*)mid2; a.x = (const unsigned short*)x; a.w3f = (const uint4*)w3f; a.w1f = (const uint4*)w1f;
   a.b3 = b3; a.b1 = b1; a.xn = (unsigned short*)x_next; a.m1 = (unsigned short*)mid1_next; a.P = (int)P;
   a.xin = nullptr; a.wpf = nullptr; a.dbg = g_chain_dbg;
+  a.H = a.W = a.Ho = a.Wo = 0;
   static relnet::PerDeviceOnce attr_once;
   if (attr_once.first()) {
     hipFuncSetAttribute((const void*)bottleneck_chain_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -541,6 +565,36 @@ extern "C" int relnet_bottleneck_chain(const void* mid2, const void* x, const vo
   return check_launch("relnet_bottleneck_chain");
 }
 
+// Last unit of a stage whose successor subsamples by two (res2c, res3b3 of the non-FPN trunk): x_next = relu(conv1x1(mid2; W3, b3) + x)
+// at the even (y, x) pixels only.  mid2 [B][Ho][Wo][mid] and x_next [B][Ho][Wo][4 mid] are compact (Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1),
+// the shortcut x [B][H][W][4 mid] is the full map (all dense NHWC bf16); x_next must not alias x.  mid = 64 or 128.  Same bits as
+// relnet_bottleneck_chain (w1f = NULL) at those pixels.
+extern "C" int relnet_bottleneck_chain_s2(const void* mid2, const void* x, const void* w3f, const float* b3, void* x_next, int B,
+                                          int H, int W, int mid, void* stream) {
+  RELNET_REQUIRE(mid2 && x && w3f && b3 && x_next && x_next != x, "relnet_bottleneck_chain_s2: null operand (or x_next == x: this form is never in place)");
+  RELNET_REQUIRE(mid == 64 || mid == 128, "relnet_bottleneck_chain_s2: mid = %d unsupported (64, 128)", mid);
+  RELNET_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W * 8 * mid < (1L << 32),
+                 "relnet_bottleneck_chain_s2: bad geometry B=%d H=%d W=%d (the full 4 mid-channel map must stay below 4 GiB)", B, H, W);
+  ChainArgs a;
+  a.m2 = (const unsigned short*)mid2; a.x = (const unsigned short*)x; a.w3f = (const uint4*)w3f; a.w1f = nullptr;
+  a.b3 = b3; a.b1 = nullptr; a.xn = (unsigned short*)x_next; a.m1 = nullptr;
+  a.xin = nullptr; a.wpf = nullptr; a.dbg = 0;
+  a.H = H; a.W = W; a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
+  const long P = (long)B * a.Ho * a.Wo;
+  a.P = (int)P;
+  static relnet::PerDeviceOnce attr_once;
+  if (attr_once.first()) {
+    hipFuncSetAttribute((const void*)bottleneck_chain_kernel<64, false, false, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)bottleneck_chain_kernel<128, true, false, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  }
+  const long ntile = (P + 31) / 32;
+  const unsigned grid = (unsigned)(ntile < 8 * 256 ? (ntile + 7) / 8 : 256);
+  const size_t lds = 65536 + 65536 + (size_t)5 * mid * 4;       // as relnet_bottleneck_chain
+  if (mid == 64) bottleneck_chain_kernel<64, false, false, 1, false, true><<<grid, 512, lds, (hipStream_t)stream>>>(a);
+  else bottleneck_chain_kernel<128, true, false, 1, false, true><<<grid, 512, lds, (hipStream_t)stream>>>(a);
+  return check_launch("relnet_bottleneck_chain_s2");
+}
+
 // First unit of res2 (projection shortcut, stride 1): x_next = relu(conv1x1(mid2; W3) + conv1x1(x_in; Wp) + b3p), b3p = b3 + bp, and
 // (optionally) mid1_next = relu(conv1x1(x_next; W1n, b1n)) in one kernel: the branch1 convolution of the reference graph
 // (resnet_v1_101_rcnn_base.py: res2a_branch1 + bn2a_branch1) becomes four more k-steps of the expand product.  mid = 64 only;
@@ -556,6 +610,7 @@ extern "C" int relnet_bottleneck_chain_proj(const void* mid2, const void* x_in, 
   a.m2 = (const unsigned short*)mid2; a.x = nullptr; a.w3f = (const uint4*)w3f; a.w1f = (const uint4*)w1f;
   a.b3 = b3p; a.b1 = b1; a.xn = (unsigned short*)x_next; a.m1 = (unsigned short*)mid1_next; a.P = (int)P;
   a.xin = (const unsigned short*)x_in; a.wpf = (const uint4*)wpf; a.dbg = 0;
+  a.H = a.W = a.Ho = a.Wo = 0;
   static relnet::PerDeviceOnce attr_once;
   if (attr_once.first()) {
     hipFuncSetAttribute((const void*)bottleneck_chain_kernel<64, false, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -577,6 +632,12 @@ extern "C" int relnet_bottleneck_chain_proj(const void* mid2, const void* x_in, 
 // Workgroup = 8 x 32 output pixels, persistent over tiles with the next halo tile in flight; wave (c, r) owns output
 // channels 32 c .. 32 c + 31 for pixel rows 2 r, 2 r + 1.  Its 36 weight fragments (32 channels x 576) stay in VGPRs for
 // the life of the workgroup, so LDS serves only the pixel operand.
+// S2 (the stride-2 output form: res2c_branch2b when only the even pixels of res2c are read): out[b][yo][xo] = the dense result at
+// (2 yo, 2 xo), from the same 36 k-steps in the same order.  Workgroup = 4 x 32 output pixels (one row per wave: a single MFMA
+// chain), whose halo is 9 rows x 65 columns.  A row is stored de-interleaved -- its 33 even columns, then its 32 odd ones -- so that
+// the 32 lanes of a tap still read 32 CONSECUTIVE pixel slots (columns 2 l + dx at stride 2 would leave half the banks idle), rows of 65
+// slots back to back: 585 slots, 74 DMA instructions, 74 KiB per buffer.  Two of them leave no room for the output staging, which
+// therefore reuses the halo buffer the tile has just finished reading (one more workgroup barrier per tile).
 // ---------------------------------------------------------------------------------------
 namespace relnet {
 
@@ -588,15 +649,22 @@ struct Halo3Args {
   const float* bias;           // [64]
   unsigned short* out;         // [B][H][W][64]
   int B, H, W, relu;
-  int tiles_x, tiles_y;        // ceil(W / 32), ceil(H / 8)
+  int tiles_x, tiles_y;        // ceil(W / 32), ceil(H / 8)  (S2: ceil(Wo / 32), ceil(Ho / 4))
+  int Ho, Wo;                  // output map (S2: (H - 1) / 2 + 1, (W - 1) / 2 + 1; otherwise H, W)
 };
 
 constexpr int kHaloW = 34, kHaloSlots = 40;                 // halo columns used / allocated per row (5 x 8 pixels)
 constexpr int kHaloBytes = 10 * kHaloSlots * 128;           // 50 DMA instructions x 1 KiB
+constexpr int kHalo2Row = 65, kHalo2Even = 33;              // S2: slots per halo row (33 even columns | 32 odd columns)
+constexpr int kHalo2Dma = (9 * kHalo2Row + 7) / 8;          // 74 DMA instructions x 1 KiB
+constexpr int kHalo2Bytes = kHalo2Dma * 1024;
 
+template <bool S2>
 __global__ __launch_bounds__(512) void conv3x3_c64_halo_kernel(Halo3Args a) {
+  constexpr int NR = S2 ? 1 : 2;                             // output rows per wave; the tile is 4 NR rows x 32 columns
+  constexpr int HB = S2 ? kHalo2Bytes : kHaloBytes;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* sOut = smem + 2 * kHaloBytes;               // [256 px][128 B], chunk c of pixel p at slot c ^ ((p >> 1) & 7)
+  unsigned char* sOutDense = smem + 2 * HB;                  // [256 px][128 B], chunk c of pixel p at slot c ^ ((p >> 1) & 7)  (S2: the halo buffer just read)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction: keeps tile / row arithmetic on the scalar unit
   const int half = lane >> 5, l31 = lane & 31;
@@ -604,7 +672,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_halo_kernel(Halo3Args a) {
   bf16x8 wfrag[36];
 #pragma unroll
   for (int ks = 0; ks < 36; ++ks) wfrag[ks] = *(const bf16x8*)&a.wf[(chh * 36 + ks) * 64 + lane];
-  float* sBias = (float*)(sOut + 32768);                     // [64]
+  float* sBias = (float*)(smem + 2 * HB + (S2 ? 0 : 32768));   // [64]
   if (tid < 64) sBias[tid] = a.bias[tid];
   const int per_img = a.tiles_x * a.tiles_y;
   const int ntile = a.B * per_img;
@@ -621,6 +689,22 @@ __global__ __launch_bounds__(512) void conv3x3_c64_halo_kernel(Halo3Args a) {
     int ln = lane;
     asm volatile("" : "+v"(ln));                            // opaque too: the per-lane parts are recomputed per tile, not kept live
     const int r8 = ln >> 3, slot = ln & 7;
+    if constexpr (S2) {
+      const int ys = 8 * ty - 1, xs = 64 * tx - 1;           // input pixel of halo (row 0, column 0)
+#pragma unroll
+      for (int i = 0; i < (kHalo2Dma + 7) / 8; ++i) {
+        const int j = wave + 8 * i;                          // DMA instruction j: slots 8 j .. 8 j + 7 of the linear [9][65] slot order
+        if (j >= kHalo2Dma) break;
+        const int q = 8 * j + r8, hy = q / kHalo2Row, sl = q - kHalo2Row * hy;
+        const int hx = sl < kHalo2Even ? 2 * sl : 2 * (sl - kHalo2Even) + 1;
+        const int y = ys + hy, x = xs + hx;
+        const int sw = (4 * j + (r8 >> 1)) & 7;              // (q >> 1) & 7
+        const bool ok = hy < 9 && y >= 0 && y < a.H && x >= 0 && x < a.W;
+        const void* src = ok ? (const void*)(img + ((long)y * a.W + x) * 64 + ((slot ^ sw) << 3)) : (const void*)g_zero_chunk;
+        __builtin_amdgcn_global_load_lds((gas_ptr)src, (las_ptr)(buf + j * 1024), 16, 0, 0);
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
       const int j = wave + 8 * i;                            // DMA instruction j: halo row j / 5, pixel slots 8 (j % 5) ..
@@ -643,13 +727,14 @@ __global__ __launch_bounds__(512) void conv3x3_c64_halo_kernel(Halo3Args a) {
     // issued after that wait and drain during the NEXT tile's arithmetic (loads and stores share vmcnt and complete out of
     // order with respect to each other, so the only safe wait is vmcnt(0): it is placed where both have had a tile's time)
     const int tn = t + gridDim.x;
-    if (tn < ntile) issue_halo(tn, smem + (cur ^ 1) * kHaloBytes);
-    const unsigned char* hb = smem + cur * kHaloBytes;
+    if (tn < ntile) issue_halo(tn, smem + (cur ^ 1) * HB);
+    const unsigned char* hb = smem + cur * HB;
+    unsigned char* sOut = S2 ? smem + cur * HB : sOutDense;
     int lq = l31;
     asm volatile("" : "+v"(lq));                            // the 72 swizzled read offsets are recomputed per tile, not held in VGPRs
-    f32x16 acc[2];
+    f32x16 acc[NR];
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
+    for (int rr = 0; rr < NR; ++rr)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[rr][r] = 0.f;
     {
@@ -657,24 +742,29 @@ __global__ __launch_bounds__(512) void conv3x3_c64_halo_kernel(Halo3Args a) {
       // of step s + 2 are requested before the MFMAs of step s
       auto frag = [&](int s_, int rr) -> bf16x8 {
         const int tap = s_ >> 2, kb = s_ & 3, dy = tap / 3, dx = tap % 3;
-        const int hp = (2 * rg + rr + dy) * kHaloSlots + lq + dx;
+        const int hp = S2 ? (2 * rg + dy) * kHalo2Row + lq + (dx == 1 ? kHalo2Even : dx >> 1)      // column 2 l + dx of row 2 rg + dy
+                          : (2 * rg + rr + dy) * kHaloSlots + lq + dx;
         return *(const bf16x8*)(hb + hp * 128 + (((2 * kb + half) ^ ((hp >> 1) & 7)) << 4));
       };
-      bf16x8 pq[3][2];
-      pq[0][0] = frag(0, 0); pq[0][1] = frag(0, 1);
-      pq[1][0] = frag(1, 0); pq[1][1] = frag(1, 1);
+      bf16x8 pq[3][NR];
+#pragma unroll
+      for (int rr = 0; rr < NR; ++rr) { pq[0][rr] = frag(0, rr); pq[1][rr] = frag(1, rr); }
 #pragma unroll
       for (int s_ = 0; s_ < 36; ++s_) {
-        if (s_ + 2 < 36) { pq[(s_ + 2) % 3][0] = frag(s_ + 2, 0); pq[(s_ + 2) % 3][1] = frag(s_ + 2, 1); }
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[s_], pq[s_ % 3][0], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[s_], pq[s_ % 3][1], acc[1], 0, 0, 0);
+        if (s_ + 2 < 36) {
+#pragma unroll
+          for (int rr = 0; rr < NR; ++rr) pq[(s_ + 2) % 3][rr] = frag(s_ + 2, rr);
+        }
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) acc[rr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[s_], pq[s_ % 3][rr], acc[rr], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+    if constexpr (S2) __builtin_amdgcn_s_barrier();         // every wave has read this halo: it becomes the output staging
     // bias -> ReLU -> bf16 -> staging [pixel][64 channels]
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-      const int p = (2 * rg + rr) * 32 + l31;
+    for (int rr = 0; rr < NR; ++rr) {
+      const int p = (NR * rg + rr) * 32 + l31;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 bq = *(const float4*)(sBias + chh * 32 + 8 * g + 4 * half);
@@ -687,16 +777,19 @@ __global__ __launch_bounds__(512) void conv3x3_c64_halo_kernel(Halo3Args a) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // both channel halves of every pixel are staged
     {
       const int b = t / per_img, ty = (t % per_img) / a.tiles_x, tx = t % a.tiles_x;
-      unsigned short* img = a.out + (long)b * a.H * a.W * 64;
-      const unsigned char* so = sOut + wave * 4096 + lane * 16;
-      const uint4 v0 = *(const uint4*)so, v1 = *(const uint4*)(so + 1024), v2 = *(const uint4*)(so + 2048), v3 = *(const uint4*)(so + 3072);
+      unsigned short* img = a.out + (long)b * a.Ho * a.Wo * 64;
+      const unsigned char* so = sOut + wave * (2048 * NR) + lane * 16;
+      const uint4 v0 = *(const uint4*)so, v1 = *(const uint4*)(so + 1024);
+      uint4 v2 = v0, v3 = v1;
+      if constexpr (NR == 2) { v2 = *(const uint4*)(so + 2048); v3 = *(const uint4*)(so + 3072); }
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       // next halo landed (this wave's part); staging read
       auto put = [&](int i, const uint4& v) {
-        const int p = 8 * (wave * 4 + i) + (lane >> 3), slot = lane & 7;
-        const int y = ty * 8 + (p >> 5), x = tx * 32 + (p & 31);
-        if (y < a.H && x < a.W) *(uint4*)(img + ((long)y * a.W + x) * 64 + ((slot ^ ((p >> 1) & 7)) << 3)) = v;
+        const int p = 8 * (wave * 2 * NR + i) + (lane >> 3), slot = lane & 7;
+        const int y = ty * 4 * NR + (p >> 5), x = tx * 32 + (p & 31);
+        if (y < a.Ho && x < a.Wo) *(uint4*)(img + ((long)y * a.Wo + x) * 64 + ((slot ^ ((p >> 1) & 7)) << 3)) = v;
       };
-      put(0, v0); put(1, v1); put(2, v2); put(3, v3);
+      put(0, v0); put(1, v1);
+      if constexpr (NR == 2) { put(2, v2); put(3, v3); }
     }
     __builtin_amdgcn_s_barrier();                           // every wave's part of the next halo is in LDS; staging is free
   }
@@ -713,15 +806,36 @@ extern "C" int relnet_conv3x3_c64(const void* in, const void* w_frag, const floa
   Halo3Args a;
   a.in = (const unsigned short*)in; a.wf = (const uint4*)w_frag; a.bias = bias; a.out = (unsigned short*)out;
   a.B = B; a.H = H; a.W = W; a.relu = relu;
-  a.tiles_x = (W + 31) / 32; a.tiles_y = (H + 7) / 8;
+  a.tiles_x = (W + 31) / 32; a.tiles_y = (H + 7) / 8; a.Ho = H; a.Wo = W;
   static relnet::PerDeviceOnce attr_once;
   if (attr_once.first()) {
-    hipFuncSetAttribute((const void*)conv3x3_c64_halo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)conv3x3_c64_halo_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   const long ntile = (long)B * a.tiles_x * a.tiles_y;
   const unsigned grid = (unsigned)(ntile < 256 ? ntile : 256);
-  conv3x3_c64_halo_kernel<<<grid, 512, 2 * kHaloBytes + 32768 + 256, (hipStream_t)stream>>>(a);
+  conv3x3_c64_halo_kernel<false><<<grid, 512, 2 * kHaloBytes + 32768 + 256, (hipStream_t)stream>>>(a);
   return check_launch("relnet_conv3x3_c64");
+}
+
+// The same convolution at stride 2: out [B][Ho][Wo][64], Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, out[b][yo][xo] = the stride-1 result at
+// (2 yo, 2 xo), bit for bit (same k-steps, same order).  Operands as relnet_conv3x3_c64.
+extern "C" int relnet_conv3x3_c64_s2(const void* in, const void* w_frag, const float* bias, int relu, void* out, int B, int H,
+                                     int W, void* stream) {
+  RELNET_REQUIRE(in && w_frag && bias && out, "relnet_conv3x3_c64_s2: null operand");
+  RELNET_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 31), "relnet_conv3x3_c64_s2: bad geometry B=%d H=%d W=%d", B, H, W);
+  Halo3Args a;
+  a.in = (const unsigned short*)in; a.wf = (const uint4*)w_frag; a.bias = bias; a.out = (unsigned short*)out;
+  a.B = B; a.H = H; a.W = W; a.relu = relu;
+  a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
+  a.tiles_x = (a.Wo + 31) / 32; a.tiles_y = (a.Ho + 3) / 4;
+  static relnet::PerDeviceOnce attr_once;
+  if (attr_once.first()) {
+    hipFuncSetAttribute((const void*)conv3x3_c64_halo_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  }
+  const long ntile = (long)B * a.tiles_x * a.tiles_y;
+  const unsigned grid = (unsigned)(ntile < 256 ? ntile : 256);
+  conv3x3_c64_halo_kernel<true><<<grid, 512, 2 * kHalo2Bytes + 256, (hipStream_t)stream>>>(a);
+  return check_launch("relnet_conv3x3_c64_s2");
 }
 
 // (Measured and dropped: the same halo-resident form for the 256-channel res4 3x3 layers -- halo tile per 64- or 128-channel

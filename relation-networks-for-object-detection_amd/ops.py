@@ -662,6 +662,18 @@ def conv3x3_halo(x, w_frag, bias, relu=True):
     return out
 
 
+def conv3x3_halo_s2(x, w_frag, bias, relu=True):
+    """conv3x3_halo at stride 2: [B,H,W,C] -> [B,(H-1)//2+1,(W-1)//2+1,C], equal bit for bit to conv3x3_halo(...)[:, ::2, ::2] (the same
+    k-steps in the same order) for a quarter of its arithmetic and output bytes.  C = 64."""
+    _chk(x, w_frag, bias)
+    B, H, W, C = x.shape
+    assert C == 64 and x.is_contiguous() and x.dtype == torch.bfloat16 and bias.dtype == torch.float32
+    assert w_frag.numel() == 9 * C * C
+    out = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), device=x.device, dtype=x.dtype)
+    _lib.call('relnet_conv3x3_c64_s2', x.data_ptr(), w_frag.data_ptr(), bias.data_ptr(), int(relu), out.data_ptr(), B, H, W, _stream())
+    return out
+
+
 def conv3x3_c64(x, w_frag, bias, relu=True):
     return conv3x3_halo(x, w_frag, bias, relu)
 
@@ -719,6 +731,25 @@ def bottleneck_chain(mid2, x, w3_frag, w1_frag, b3, b1, inplace=False):
     _lib.call('relnet_bottleneck_chain', mid2.data_ptr(), x.data_ptr(), w3_frag.data_ptr(), _ptr(w1_frag), b3.data_ptr(),
               _ptr(b1), xn.data_ptr(), _ptr(m1), mid2.numel() // mid, mid, _stream())
     return xn, m1
+
+
+CHAIN_S2_MIDS = (64, 128)        # widths of the expand-only form that gathers its shortcut at stride 2 (the last units of res2 / res3)
+
+
+def bottleneck_chain_s2(mid2, x, w3_frag, b3):
+    """x_next = relu(conv1x1(mid2; W3, b3) + x[:, ::2, ::2]) for a unit whose output only stride-2 1x1 layers read: mid2 [B,Ho,Wo,mid] is
+    the compact map of the even pixels (Ho = (H-1)//2+1, Wo = (W-1)//2+1), x [B,H,W,4 mid] the full shortcut map, gathered inside the
+    kernel.  -> x_next [B,Ho,Wo,4 mid] (never in place), bit for bit bottleneck_chain(...)[0][:, ::2, ::2] of the dense operands."""
+    _chk(mid2, x, w3_frag, b3)
+    mid = mid2.shape[-1]
+    B, H, W, C = x.shape
+    assert mid in CHAIN_S2_MIDS and C == 4 * mid and mid2.shape == (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, mid)
+    assert mid2.is_contiguous() and x.is_contiguous() and x.numel() * 2 < (1 << 32)
+    assert mid2.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and b3.dtype == torch.float32
+    xn = torch.empty(mid2.shape[:-1] + (C,), device=x.device, dtype=x.dtype)
+    _lib.call('relnet_bottleneck_chain_s2', mid2.data_ptr(), x.data_ptr(), w3_frag.data_ptr(), b3.data_ptr(), xn.data_ptr(), B, H, W, mid,
+              _stream())
+    return xn
 
 
 def bottleneck_chain_proj(mid2, x_in, w3_frag, wp_frag, w1_frag, b3p, b1):
