@@ -120,6 +120,9 @@ void relnet_gemm_debug_phase_ts(void* buf); /* measurement knob: the ring kernel
 void relnet_gemm_debug_ablate(int a);     /* measurement knob for tile 8: 1 = fill path only, 2 = LDS + MFMA only (garbage results) */
 void relnet_chain_debug(int flags);        /* measurement knob for chain256_roles_kernel (garbage results while non-zero): 1 = half of the weight loads, 2 = none, 4 = no shortcut-slice loads, 8 = no global stores */
 int relnet_gemm_tile_count(void);         /* number of tile configurations (valid relnet_gemm_force_tile values 1..count) */
+int relnet_gemm_last_launch(void);        /* what the last bf16-operand relnet_gemm_nt / relnet_conv2d_nhwc(_wf) launch ran, for tests: low byte 1 = LDS-tiled,
+                                           * 2 = ring, 3 = ring with the window schedule, 4 = ring with a hand-scheduled k-loop, 5 = row panel, 6 = split-K;
+                                           * bits 8.. = ways the k-loop was split (1 = not).  A forced tile falls back on shapes it is not written for. */
 /* Work area of the split-K tile (configuration 23, round 6: launches of at most one 64 x 64 workgroup per CU with a long k-loop -- fc_new_1 and
  * rpn_conv_3x3 of the one-image step of core/tester.py:219-295 / train_end2end.py with BATCH_IMAGES: 1 -- split their k-loop over 3..4 workgroups per
  * tile; fp32 partial tiles and per-tile arrival counters live here).  `ws`: device memory owned by the caller, 256-byte aligned, its first 16 KB

@@ -2089,6 +2089,11 @@ static long long* g_phase_ts = nullptr;   // measurement knob: ring kernels writ
 extern "C" void relnet_gemm_debug_phase_ts(void* buf) { g_phase_ts = (long long*)buf; }
 static int g_asm = 1;            // tuning knob: 0 = pick_tile never chooses tiles 18 / 19 (hand-scheduled k-loops)
 extern "C" void relnet_gemm_debug_asm(int on) { g_asm = on; }
+// what the last bf16-operand GEMM / convolution launch of this process ran (a forced tile runs its fallback on shapes it is not written for, a
+// split-K launch runs unsplit without room in the work area): kernel kind in the low byte, split-K ways above it.  For tests.
+enum { LK_TILED = 1, LK_RING = 2, LK_WINDOW = 3, LK_ASM = 4, LK_PANEL = 5, LK_SPLITK = 6 };
+static int g_last_launch = 0;
+extern "C" int relnet_gemm_last_launch(void) { return g_last_launch; }
 
 // ---- split-K work area (relnet_gemm_set_workspace): 16 KB of tile counters (zero between launches) + fp32 partial tiles.  The area is the CALLER's:
 // the launches that share one must be ordered (one stream, or the dependencies of one captured graph), so the host side (ops.py) keeps one area per
@@ -2136,6 +2141,7 @@ static void launch_cfg(GemmArgs g, int batch, int out_dtype, hipStream_t s, int 
     const long tiles = (long)ntile * ((g.M + BM - 1) / BM);
     if (batch == 1 && splitk_area((long)ksplit * g.M * g.N * 4, tiles, &g.kpart, &g.kcnt)) {
       g.ksplit = ksplit; g.n_loop = 1;
+      g_last_launch = LK_SPLITK | (ksplit << 8);
       dim3 grid(ntile, (g.M + BM - 1) / BM, ksplit);
       g.xcd_swizzle = (g_swizzle && ntile > 1 && tiles >= 16) ? 1 : 0;
       if (out_dtype == RELNET_BF16) gemm_nt_bf16_kernel<BM, BN, WM, WN, unsigned short, CONV, KU><<<grid, 64 * WM * WN, 0, s>>>(g);
@@ -2152,6 +2158,7 @@ static void launch_cfg(GemmArgs g, int batch, int out_dtype, hipStream_t s, int 
   if (nloop < 1) nloop = 1;
   if (nloop > ntile) nloop = ntile;
   g.n_loop = nloop;
+  g_last_launch = LK_TILED | (1 << 8);
   dim3 grid((ntile + nloop - 1) / nloop, (g.M + BM - 1) / BM, batch);
   g.xcd_swizzle = (swz && grid.x > 1) ? 1 : 0;
   if (out_dtype == RELNET_BF16) gemm_nt_bf16_kernel<BM, BN, WM, WN, unsigned short, CONV, KU><<<grid, 64 * WM * WN, 0, s>>>(g);
@@ -2175,6 +2182,8 @@ static void launch_ring(GemmArgs g, int batch, int out_dtype, hipStream_t s) {
   g.xcd_swizzle = (swz && grid.x > 1) ? 1 : 0;
   g.korder = 0;
   g.phase_ts = g_phase_ts;
+  // (a shortcut launch runs the plain schedule whatever SCHED says, see below)
+  g_last_launch = (g.resid ? LK_RING : SCHED == 4 ? LK_WINDOW : (SCHED == 5 || SCHED == 6) ? LK_ASM : LK_RING) | (1 << 8);
   if constexpr (CONV == 1) {
     // Spatial convolutions re-read every input pixel once per tap.  In (tap, channel chunk) order the re-reads of one workgroup are
     // R * S k-slabs apart and the 32 resident workgroups of an XCD stream ~24 MB in between: the 4 MiB L2 has long dropped the
@@ -2228,7 +2237,7 @@ static void launch_ring(GemmArgs g, int batch, int out_dtype, hipStream_t s) {
 //                                   11 = 8 with the register epilogue (no LDS band)
 //                                   12 = 8 with the fragment-pipelined schedule on shortcut-free layers
 // row-panel (gemm_panel_kernel):    13 = A panel resident, all column tiles per workgroup (K in {64,128,256,512}, N % 256 == 0,
-//                                        bf16 out, 1x1 / plain GEMM); other shapes under 13 run configuration 1
+//                                        bf16 out, 1x1 / plain GEMM, no per-row bias); other shapes under 13 run configuration 1
 //                                   14 = the same with W streamed from its fragment-order copy through registers
 //                                        (gemm_panelw_kernel; needs the Wf operand, else configuration 13)
 //                                   15 = 14 with 64-row panels, two workgroups per CU
@@ -2251,6 +2260,7 @@ template <int CONV>
 static bool launch_panel(const GemmArgs& g0, int batch, int out_dtype, hipStream_t s, bool use_wf = false, bool occ2 = false) {
   GemmArgs g = g0;
   if (batch != 1 || out_dtype != RELNET_BF16 || g.N % 256 != 0 || (g.ldc & 7)) return false;
+  if (g.bias_mode == 2) return false;                    // the panel epilogues add the per-column bias only
   if constexpr (CONV == 2) return false;
   if constexpr (CONV == 1) {                             // 1x1, stride 1, no padding: a plain GEMM over the pixels
     if (g.cR != 1 || g.cS != 1 || g.cStride != 1 || g.cPad != 0) return false;
@@ -2258,6 +2268,7 @@ static bool launch_panel(const GemmArgs& g0, int batch, int out_dtype, hipStream
     g.lda = g.cPix;
   }
   const bool res = g.resid != nullptr;
+  g_last_launch = LK_PANEL | (1 << 8);                   // (a K no panel kernel takes: the caller's fallback overwrites it)
   if (use_wf && g.Wf && occ2) {
 #define RELNET_PANELW2(KP_)                                                                            \
   do {                                                                                                  \

@@ -126,6 +126,7 @@ _SIGNATURES = {
     'relnet_gemm_debug_ablate': (None, [_i]),
     'relnet_chain_debug': (None, [_i]),
     'relnet_gemm_tile_count': (C.c_int, []),
+    'relnet_gemm_last_launch': (C.c_int, []),
     'relnet_gemm_set_workspace': (C.c_int, [_vp, _l]),
     'relnet_roi_pool_bwd_cl': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'relnet_roi_pool_bwd_debug': (None, [_i]),
