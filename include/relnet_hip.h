@@ -225,6 +225,10 @@ int relnet_relation_attention_kc(const void* q, long q_ld, long q_bs, const void
 /* tuning / test knob: 1 (default, round 6) = a bf16 launch with a FLOAT32 bias (ln G: the training forward) runs on the LDS-resident kernel like the fp16-bias
  * inference launches (no logits output); 0 = on the streaming kernel of rounds 1 - 5 */
 void relnet_relation_attention_debug_lds_f32(int on);
+/* which kernel the last relnet_relation_attention(_kc / _fused) call launched (the last launch ATTEMPTED: it is recorded before the launch is
+ * checked; one process-wide value, not synchronised), for tests: 1 = streaming fp32, 2 = streaming bf16 (fp32 bias),
+ * 3 = LDS kernel with the fp16 log2 G bias, 4 = LDS kernel with the float32 ln G bias, 5 = fused geometry + attention; 0 = none yet */
+int relnet_relation_attention_last_launch(void);
 
 /* Geometry + attention of ONE relation module in a single kernel (bf16 throughput path; csrc/relation.hip:
  * relation_fused_kernel): the position embedding (SYM_REL:29-83), pair_pos_fc1 + ReLU + log (:109-116, :139) and the

@@ -364,6 +364,14 @@ __global__ __launch_bounds__(256) void relation_attention_kernel(AttnArgs a) {
           bf16x8 vf;
           *(uint2*)&vf = *(const uint2*)(Vr);
           *((uint2*)&vf + 1) = *(const uint2*)(Vr + 8);
+          if (key0 + 32 > Mb) {                          // keys past the image's count: P is 0 there, but VW^T of a padding row may be NaN / Inf (0 x NaN)
+            unsigned int* vw = (unsigned int*)&vf;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+              const int kw = key0 + 16 * ks + 8 * (w >> 1) + 4 * half + 2 * (w & 1);
+              vw[w] &= (kw < Mb ? 0xffffu : 0u) | (kw + 1 < Mb ? 0xffff0000u : 0u);
+            }
+          }
           o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[d], 0, 0, 0);
         }
       }
@@ -373,7 +381,11 @@ __global__ __launch_bounds__(256) void relation_attention_kernel(AttnArgs a) {
         const float* Vr = (const float*)Vb + (long)(32 * d + l31) * a.vwt_ld + key0 + 4 * half;
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
-          const float4 v = *(const float4*)(Vr + 8 * gq);
+          float4 v = *(const float4*)(Vr + 8 * gq);
+          if (key0 + 32 > Mb) {                          // as above: an exact zero for the keys past the image's count, whatever VW^T holds there
+            const int kv = key0 + 8 * gq + 4 * half;
+            v.x = kv < Mb ? v.x : 0.f; v.y = kv + 1 < Mb ? v.y : 0.f; v.z = kv + 2 < Mb ? v.z : 0.f; v.w = kv + 3 < Mb ? v.w : 0.f;
+          }
           o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.x, s[4 * gq + 0], o[d], 0, 0, 0);
           o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.y, s[4 * gq + 1], o[d], 0, 0, 0);
           o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.z, s[4 * gq + 2], o[d], 0, 0, 0);
@@ -475,6 +487,20 @@ __global__ __launch_bounds__(1024) void relation_attention_lds_kernel(AttnArgs a
   for (int kc0 = 0; kc0 < a.M; kc0 += kKC) {
     if (kc0 > 0) __syncthreads();
     const int clen = min(a.M - kc0, kKC);             // valid keys of this chunk
+    // key_count: only the columns of the image's own keys are staged, the rest of the chunk stays zero (or, in a later chunk, what an earlier one
+    // staged) -- P is 0 for the keys of padding rows, but their VW^T may hold NaN / Inf, and 0 x NaN is not 0
+    const int clenv = min(max(Mb - kc0, 0), clen);
+    const int v4 = (clenv + 3) >> 2;                  // 4-key groups per row
+    const int v4f = clenv >> 2;                       // ... of which full ones (staged by the loop further down)
+    if ((clenv & 3) && tid < 64) {                    // the partial last group, one row per thread: the columns past the last key become zeros
+      const int rem = clenv & 3;
+      int row = tid;
+      asm volatile("" : "+v"(row));                   // keeps the row address inside the loop: hoisted, it costs the register the staging loops lack
+      uint2 v = *(const uint2*)(Vb + (long)row * a.vwt_ld + kc0 + 4 * v4f);
+      v.x &= rem >= 2 ? 0xffffffffu : 0xffffu;
+      v.y &= rem == 3 ? 0xffffu : 0u;
+      *(uint2*)(sV + row * vld + 4 * v4f) = v;
+    }
     // bias of the first tile: issued before the staging so that its latency overlaps it
     BV bcur[4];
 #pragma unroll
@@ -495,7 +521,6 @@ __global__ __launch_bounds__(1024) void relation_attention_lds_kernel(AttnArgs a
         if (c < clen * 8) *(uint4*)(sK + row * 128 + ((ch ^ (row & 7)) << 4)) = kq[i];
       }
     }
-    const int v4 = (clen + 3) >> 2;                   // 4-key groups per row
     // zero what the masked tail of the last tile may touch (P is 0 there, but 0 x NaN is not)
     if (kc0 == 0) {
       for (int c = tid; c < 64 * ((vld >> 2) - v4); c += nthr) {
@@ -504,17 +529,17 @@ __global__ __launch_bounds__(1024) void relation_attention_lds_kernel(AttnArgs a
       }
       if (tid < 16) *(uint2*)(sV + 64 * vld + 4 * tid) = make_uint2(0, 0);
     }
-    for (int c0 = tid; c0 < 64 * v4; c0 += 4 * nthr) {
+    for (int c0 = tid; c0 < 64 * v4f; c0 += 4 * nthr) {
       uint2 vq[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int c = min(c0 + i * nthr, 64 * v4 - 1), row = c / v4, c4 = c - row * v4;
+        const int c = min(c0 + i * nthr, 64 * v4f - 1), row = c / v4f, c4 = c - row * v4f;
         vq[i] = *(const uint2*)(Vb + (long)row * a.vwt_ld + kc0 + 4 * c4);   // pad cols are 0
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int c = c0 + i * nthr, row = c / v4, c4 = c - row * v4;
-        if (c < 64 * v4) *(uint2*)(sV + row * vld + 4 * c4) = vq[i];
+        const int c = c0 + i * nthr, row = c / v4f, c4 = c - row * v4f;
+        if (c < 64 * v4f) *(uint2*)(sV + row * vld + 4 * c4) = vq[i];
       }
     }
     __syncthreads();
@@ -957,6 +982,8 @@ extern "C" int relnet_geometry_bias(const float* boxes, int box_stride, int box_
 
 static int g_attn_lds_f32 = 1;     // tuning / test knob: 1 = bf16 attention with a float32 bias runs on the LDS kernel, 0 = on the streaming kernel (rounds 1 - 5)
 extern "C" void relnet_relation_attention_debug_lds_f32(int on) { g_attn_lds_f32 = on; }
+static int g_attn_last_launch = 0; // for tests, the last launch attempted: 1 streaming fp32, 2 streaming bf16, 3 LDS kernel fp16 bias, 4 LDS kernel float32 bias, 5 fused
+extern "C" int relnet_relation_attention_last_launch(void) { return g_attn_last_launch; }
 
 extern "C" int relnet_relation_attention_kc(
     const void* q, long q_ld, long q_bs, const void* k, long k_ld, long k_bs, const void* vwt,
@@ -1005,13 +1032,16 @@ extern "C" int relnet_relation_attention_kc(
     dim3 g2((unsigned)((qtiles + nwave - 1) / nwave), H, B);
     if (bias_half) relation_attention_lds_kernel<false><<<g2, nwave * 64, lds, s>>>(a, kc_rows, vld);
     else relation_attention_lds_kernel<true><<<g2, nwave * 64, lds, s>>>(a, kc_rows, vld);
+    g_attn_last_launch = bias_half ? 3 : 4;
   } else if (in_dtype == RELNET_BF16) {
     RELNET_REQUIRE(q_ld % 8 == 0 && k_ld % 8 == 0 && vwt_ld % 4 == 0, "relnet_relation_attention(bf16): row strides must be 16-byte (q,k) / 8-byte (vwt) aligned");
     relation_attention_kernel<unsigned short, unsigned short><<<grid, 256, 0, s>>>(a);
+    g_attn_last_launch = 2;
   } else if (in_dtype == RELNET_F32) {
     RELNET_REQUIRE(!bias_half, "relnet_relation_attention(f32): fp32 bias required");
     RELNET_REQUIRE(q_ld % 4 == 0 && k_ld % 4 == 0 && vwt_ld % 4 == 0, "relnet_relation_attention(f32): row strides must be 16-byte aligned");
     relation_attention_kernel<float, float><<<grid, 256, 0, s>>>(a);
+    g_attn_last_launch = 1;
   } else {
     RELNET_REQUIRE(false, "relnet_relation_attention: unknown dtype %d", in_dtype);
   }
@@ -1064,5 +1094,6 @@ extern "C" int relnet_relation_attention_fused(
   }
   const unsigned grid = (unsigned)(f.nq * ((B + 7) / 8) * 8);
   relation_fused_kernel<<<grid, 1024, lds, (hipStream_t)stream>>>(f);
+  g_attn_last_launch = 5;
   return check_launch("relnet_relation_attention_fused");
 }

@@ -228,7 +228,8 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_q_kernel(AttnBwdAr
   Frag<T> qf, dyf;
   qf.load(Qr, half);
   dyf.load(dYr, half);
-  // D = sum_d dY (Y - bout) over this lane's half of the 64 channels, then across the two halves
+  // bf16: D = sum_d dY (Y - bout) over this lane's half of the 64 channels, then across the two halves.  float32: D = sum_j p_j ds_j, formed in
+  // pass 1 below; that instantiation reads neither a.y nor a.bout
   float D = 0.f;
   if constexpr (sizeof(T) == 2) {
 #pragma unroll
@@ -240,23 +241,21 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_q_kernel(AttnBwdAr
         D += dyf.get(kk, j) * (bf2f((unsigned short)yv[j]) - (a.bout ? a.bout[h * 64 + d] : 0.f));
       }
     }
-  } else {
-#pragma unroll
-    for (int s = 0; s < 32; ++s) {
-      const int d = half * 32 + s;
-      D += dyf.f[s] * (((const float*)Yr)[d] - (a.bout ? a.bout[h * 64 + d] : 0.f));
-    }
+    D += __shfl_xor(D, 32);
   }
-  D += __shfl_xor(D, 32);
 
   const int nkt = (a.M + 31) / 32;
   const int Mb = a.key_count ? min(max(a.key_count[b], 1), a.M) : a.M;
-  // pass 1: row maximum and normaliser
-  float m_run = -INFINITY, l_run = 0.f;
+  // pass 1: row maximum and normaliser.  float32 (the parity path): D is re-derived here as sum_j p_j ds_j from the SAME p and ds that pass 2
+  // forms, instead of dY . (y - bout) from the stored output -- then sum_j dL_j = sum_j p_j (ds_j - D) cancels to rounding of the terms themselves
+  // (exactly 0 with one key), where the output's own rounding left a residue of ~1e-6 |ds| that the geometry backward multiplies by 1 / G
+  float m_run = -INFINITY, l_run = 0.f, d_run = 0.f;
   for (int kt = 0; kt < nkt; ++kt) {
     const int key0 = kt * 32;
     int kr = key0 + l31; kr = kr < a.M ? kr : a.M - 1;
     f32x16 s = dot64<T>(Kb + (long)kr * a.k_ld, qf, half);
+    f32x16 ds1;
+    if constexpr (sizeof(T) == 4) ds1 = dot64<T>(VWb + (long)kr * a.vw_ld, dyf, half);
     float tmax = -INFINITY;
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
@@ -273,13 +272,20 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_q_kernel(AttnBwdAr
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
     const float m_new = fmaxf(m_run, tmax);
-    float psum = 0.f;
+    float psum = 0.f, dsum = 0.f;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) psum += sm_exp<T>(s[r] - m_new);
-    l_run = l_run * sm_exp<T>(m_run - m_new) + psum;
+    for (int r = 0; r < 16; ++r) {
+      const float e = sm_exp<T>(s[r] - m_new);
+      psum += e;
+      if constexpr (sizeof(T) == 4) dsum += (s[r] == -INFINITY) ? 0.f : e * ds1[r];      // masked keys: an exact zero whatever ds holds
+    }
+    const float alpha = sm_exp<T>(m_run - m_new);
+    l_run = l_run * alpha + psum;
+    if constexpr (sizeof(T) == 4) d_run = d_run * alpha + dsum;
     m_run = m_new;
   }
   const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
+  if constexpr (sizeof(T) == 4) D = (d_run + __shfl_xor(d_run, 32)) * inv;
 
   // pass 2: S, dS, dL, dQ
   f32x16 o[2];

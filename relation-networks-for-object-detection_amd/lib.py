@@ -132,6 +132,7 @@ _SIGNATURES = {
     'relnet_roi_pool_bwd_debug': (None, [_i]),
     'relnet_deformable_col2im_debug': (None, [_i]),
     'relnet_relation_attention_debug_lds_f32': (None, [_i]),
+    'relnet_relation_attention_last_launch': (C.c_int, []),
     'relnet_deformable_psroi_pool_bwd_debug': (None, [_i]),
     'relnet_stream_capture_id': (C.c_ulonglong, [_vp]),
     'relnet_gemm_debug_splitk': (None, [_i]),

@@ -192,7 +192,9 @@ def relation_attention(q, k, vwt, bias, bout=None, resid=None, M=None, want_out=
                        want_act=False, want_logits=False, heads=16, key_count=None):
     """q [B,N,>=H*64] (row stride free), k [B,>=M,..], vwt [B,H*64,Mpad] (zero padded),
     bias [B,H,N,Mpad] fp32 -> (out [B,N,H*64] | None, relu(resid+out) | None, logits | None).
-    key_count [B] int32 (optional): image b has only key_count[b] <= M keys, the rest of its key rows are padding."""
+    key_count [B] int32 (optional): image b has only key_count[b] <= M keys, the rest of its key rows are padding and contribute an exact zero
+    whatever they (and their VW^T / bias columns) hold, NaN and Inf included.  Every kernel clamps the count to min(max(key_count[b], 1), M): a
+    count of 0 behaves as 1, a count above M as M."""
     _chk(q, k, vwt, bias, bout, resid, key_count)
     assert key_count is None or (key_count.dtype == torch.int32 and key_count.is_contiguous() and key_count.numel() == q.shape[0])
     B, N = q.shape[0], q.shape[1]
@@ -1536,7 +1538,9 @@ def relation_bwd_small_ok(dtype, N, Mpad):
 
 def relation_attention_bwd(q, k, kt, vw, bias, dy, y, bout, qt, dyt, M, heads=16, key_count=None, packed_out=None):
     """Adjoint of relation_attention: -> (dq [B,N,H*64], dk [B,M,H*64], dvw [B,M,H*64], prob | None, dlog [B,H,N,Mpad]), fp32
-    (prob is None on the small-N path: S never leaves LDS there)."""
+    (prob is None on the small-N path: S never leaves LDS there).
+    key_count [B] int32 (optional) as in relation_attention, clamped the same way: min(max(key_count[b], 1), M), so 0 behaves as 1 and a count
+    above M as M.  Unlike the forward, the backward needs FINITE padding rows (attention_module_backward)."""
     _chk(q, k, kt, vw, bias, dy, y, bout, qt, dyt, key_count)
     B, N = q.shape[0], q.shape[1]
     H = heads

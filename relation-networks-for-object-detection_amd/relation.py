@@ -200,7 +200,10 @@ def attention_module_backward(roi_feat, rois, params, d_out, nongt_dim=None, ind
 
     Every contraction runs on the GEMM / attention kernels: weight gradients are A^T B products, formed as
     gemm_nt over transposed copies (relnet_transpose_2d); the forward is recomputed from roi_feat (nothing but
-    the inputs has to be kept alive between forward and backward)."""
+    the inputs has to be kept alive between forward and backward).
+
+    key_count: padding rows stay finite in the backward.  Parameter gradients are sums over all rows, formed in GEMMs outside these kernels, and a
+    zero `d_out` times a NaN feature is NaN there.  (The forward takes arbitrary padding rows.)"""
     squeeze = roi_feat.dim() == 2
     f = roi_feat[None] if squeeze else roi_feat
     bx = (rois[None] if rois.dim() == 2 else rois).to(torch.float32).contiguous()
@@ -213,7 +216,8 @@ def attention_module_backward(roi_feat, rois, params, d_out, nongt_dim=None, ind
     mod = packed or RelationParams(params, index, dtype, f.device)
     # fp32 ln G [B,16,N,Mpad] in float32 libm arithmetic and the module output y computed FROM IT (the softmax backward needs
     # D = dY.(y - bout) consistent with the softmax weights it re-derives from this G): taken from the training forward when it ran
-    # on that geometry (`cache` holds bias / y / qk / vwt), recomputed otherwise.
+    # on that geometry (`cache` holds bias / y / qk / vwt), recomputed otherwise.  (The float32 kernels re-derive D = sum_j p_j ds_j themselves and do
+    # not read y: csrc/relation_bwd.hip, relation_attention_bwd_q_kernel.)
     # Measured and rejected (r03, tools/dbg_geom.py + tests/test_gpu_train_step.py::test_fpn_training_step...): taking G from the
     # matrix-core kernel (fp16 products, hardware log / sin: |dG| <= 3e-4, 2e-5 on average) or from the forward's own fp16 bias
     # moves the pair_pos_fc1 gradient by 50 % in norm on rows whose keys are all (nearly) clamped -- there Z = sum_j G_j e^a_j is

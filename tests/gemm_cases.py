@@ -282,6 +282,10 @@ def _fill_pattern(buf):
     buf.view(_INT[buf.element_size()]).fill_(_PATTERN[buf.element_size()])
 
 
+fill_pattern = _fill_pattern            # public names for the other edge-case modules (tests/relation_edge_cases.py)
+INT_VIEW = _INT
+
+
 def guarded(shape, dtype, parent=None, index=None, device='cuda'):
     """One flat buffer filled with a fixed quiet-NaN bit pattern; the operand is `parent_tensor[index]` (default: the dense tensor of `shape`) in the
     middle of it, with max(1 MiB, 256 rows of the parent) of pattern on both sides (256-byte aligned start).  Every element of the parent the view

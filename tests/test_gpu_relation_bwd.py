@@ -98,7 +98,8 @@ def test_key_count_masks_padding_rows(dtype):
     """Fixed-size roi buffers with a different number of REAL rows per image (FPN dummy rois, short proposal lists): with
     key_count[b] the first key_count[b] rows are the keys of image b -- forward and backward must equal the same module run
     on that image alone with nongt_dim = key_count[b] (float32: to rounding of the shared GEMMs; bf16: to its tolerance),
-    whatever the padding rows contain."""
+    whatever the padding rows contain -- finite for the backward, arbitrary for the forward (NaN / Inf padding rows in the forward:
+    tests/test_gpu_relation_edges.py; the parameter gradients are sums over all rows formed in GEMMs, where 0 x NaN is NaN)."""
     import relnet_amd  # noqa: F401
     from relnet_amd import relation
     dt = torch.float32 if dtype == 'f32' else torch.bfloat16
