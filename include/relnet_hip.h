@@ -641,6 +641,39 @@ int relnet_colsum_add_grouped(const void* const* xs, const long* lds, const long
 int relnet_sgd_update(float* w, float* mom, const float* grad, void* w_bf16, long n, float lr, float momentum,
                       float wd, float rescale_grad, void* stream);
 
+/* ---- Guard of the optimizer step (csrc/guard.hip; train.GradGuard) --------------------------------------------------------------
+ * Global L2 norm and non-finite count of the gradients, the decision to skip the step, global-norm clipping
+ * (torch.nn.utils.clip_grad_norm_'s rule) and mx.optimizer.SGD's element-wise clip_gradient, all on the device: no host
+ * synchronisation, no allocation, no atomic, bitwise reproducible for the same inputs.
+ * relnet_grad_stats: n <= 16 ranges (ptrs[i], ns[i]) of float32, HOST arrays, any 4-byte aligned pointer and any ns[i] >= 1.  Range i
+ *   runs on min(ceil(ns[i] / 4096), 2048) workgroups; workgroup b of the launch writes {double sum of squares, int64 non-finite count}
+ *   of its elements to slot slot_base + b of `workspace` (16 bytes per slot, 16-byte aligned, relnet_grad_guard_workspace_bytes(slots)).
+ *   relnet_grad_stats_slots (host) = the number of slots such a launch writes, -1 on a bad table.  An inf or NaN adds to the count
+ *   and nothing to the sum; denormals are finite.
+ * relnet_grad_guard_decide: folds slots [0, n_slots) -- the slots of ALL statistics launches of the step, ordered before it by the
+ *   stream -- in a fixed order and updates *state: steps += 1, last_norm = sqrt(sum), last_nonfinite = count.  count > 0: skip = 1,
+ *   scale = 1, skipped += 1.  Otherwise skip = 0, scale = float32(min(1, max_norm / (norm + 1e-6))) (1 when max_norm <= 0 or the norm
+ *   is 0), clipped += 1 when scale < 1, norm_sum += norm, norm_max = max(norm_max, norm).
+ * relnet_sgd_update_guarded: relnet_sgd_update with the gradient term clip((rescale_grad * grad) * state->scale, +-clip_gradient)
+ *   (no clipping for clip_gradient < 0); writes NOTHING when state->skip != 0.  skip and scale are read from device memory.
+ *   Bit-identical to relnet_sgd_update when skip == 0, scale == 1.0f and clip_gradient < 0.
+ * A fresh state is all zero except scale = 1.0f.                                                                                   */
+typedef struct {
+  int skip;                       /* 1: the last decided step had a non-finite gradient element */
+  float scale;                    /* global-norm clipping factor of the last decided step */
+  double last_norm;               /* L2 norm of the (finite) gradient elements of the last decided step */
+  long long last_nonfinite;       /* its number of inf / NaN elements */
+  long long steps, skipped, clipped;
+  double norm_sum, norm_max;      /* over the steps that were not skipped */
+} relnet_grad_guard_state;        /* 64 bytes */
+long relnet_grad_guard_workspace_bytes(long slots);
+long relnet_grad_stats_slots(const long* ns, int n);
+int relnet_grad_stats(const float* const* ptrs, const long* ns, int n, void* workspace, long slot_base, long slot_capacity,
+                      void* stream);
+int relnet_grad_guard_decide(const void* workspace, long n_slots, double max_norm, void* state, void* stream);
+int relnet_sgd_update_guarded(float* w, float* mom, const float* grad, void* w_bf16, long n, float lr, float momentum, float wd,
+                              float rescale_grad, const void* state, float clip_gradient, void* stream);
+
 /* ---- DCN backward (DeformableConvolutionOp::Backward, deformable_convolution-inl.h:145-237) ---------
  * The column gradient dcol = dY W comes from relnet_gemm_nt; this entry is deformable_col2im
  * (nn/deformable_im2col.cuh:313-351) + deformable_col2im_coord (:420-470) in one pass: grad_data (fp32, logical

@@ -165,6 +165,11 @@ _SIGNATURES = {
     'relnet_metric_softmax': (C.c_int, [_vp, _vp, _l, _i, _l, _vp, _vp, _vp, _vp, _vp]),
     'relnet_metric_sum_count': (C.c_int, [_vp, _vp, _l, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp]),
     'relnet_metric_nms_acc': (C.c_int, [_vp, _vp, _l, _vp, _vp]),
+    'relnet_grad_guard_workspace_bytes': (C.c_long, [_l]),
+    'relnet_grad_stats_slots': (C.c_long, [_vp, _i]),
+    'relnet_grad_stats': (C.c_int, [_vp, _vp, _i, _vp, _l, _l, _vp]),
+    'relnet_grad_guard_decide': (C.c_int, [_vp, _l, _d, _vp, _vp]),
+    'relnet_sgd_update_guarded': (C.c_int, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _vp, _f, _vp]),
 }
 
 

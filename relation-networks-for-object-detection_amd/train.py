@@ -97,9 +97,69 @@ class _Flat(object):
         return buf[off:off + n].view(shape)
 
 
+class GradGuard(object):
+    """Device-side guard of `Trainer.update()` (csrc/guard.hip): the global L2 norm and the non-finite count of all trainable
+    gradients are measured after the all-reduce (every rank decides from the same numbers), the WHOLE update is skipped when any
+    element is inf / NaN -- master weights, momentum and bf16 copies stay bit-unchanged -- and the gradient can be clipped:
+
+      max_norm       by global norm, torch.nn.utils.clip_grad_norm_'s rule: every gradient times min(1, max_norm / (norm + 1e-6))
+      clip_gradient  element-wise, mx.optimizer.SGD's: mom = momentum mom - lr (clip(rescale_grad grad, +-c) + wd w)
+                     (with both, the global scale is applied first)
+
+    None of it synchronises with the host or allocates per step (the workspace is sized when the guard first meets a trainer's
+    ranges).  `GradGuard()` only measures and skips: a finite gradient then gives the bits of the unguarded update.  The host never
+    learns that a step was skipped: `Trainer.step_count` advances all the same, so a learning-rate schedule stays a function of the
+    number of calls.  `report()` is the one place that synchronises."""
+
+    def __init__(self, max_norm=None, clip_gradient=None):
+        assert max_norm is None or max_norm > 0, "max_norm must be positive (None: no global-norm clipping)"
+        assert clip_gradient is None or clip_gradient >= 0, "clip_gradient must not be negative (None: no element-wise clipping)"
+        self.max_norm, self.clip_gradient = max_norm, clip_gradient
+        self.state = self.workspace = None
+        self._cursor = 0
+
+    def bind(self, device):
+        """Create the guard state on `device` (done by the trainer on first use)."""
+        if self.state is None or self.state.device != torch.device(device):
+            self.state = T.grad_guard_state(device)
+            self.workspace = None
+        return self
+
+    def begin(self, slots):
+        """Start the statistics of one step that will write `slots` slots in all."""
+        if self.workspace is None or self.workspace.numel() * 8 < slots * T.GUARD_SLOT_BYTES:
+            self.workspace = T.grad_guard_workspace(slots, self.state.device)
+        self._cursor = 0
+
+    def stats(self, views):
+        for i in range(0, len(views), T.GUARD_MAX_RANGES):
+            self._cursor += T.grad_stats(views[i:i + T.GUARD_MAX_RANGES], self.workspace, self._cursor)
+
+    def decide(self):
+        T.grad_guard_decide(self.workspace, self._cursor, self.state, self.max_norm or 0.0)
+
+    def reset(self):
+        """Zero the totals (and the last step's figures)."""
+        if self.state is not None:
+            self.state.copy_(T.grad_guard_state(self.state.device))
+
+    def report(self):
+        """Totals since the last reset, read back from the device (synchronises).  mean_norm / max_norm_seen are over the steps that
+        were not skipped; last_norm is the norm of the finite elements when the last step was skipped."""
+        if self.state is None:
+            return {'steps': 0, 'skipped': 0, 'clipped': 0, 'last_norm': 0.0, 'last_nonfinite': 0, 'mean_norm': 0.0, 'max_norm_seen': 0.0}
+        s = self.state.cpu()
+        f = s.view(torch.float64)
+        steps, skipped, clipped = int(s[3]), int(s[4]), int(s[5])
+        return {'steps': steps, 'skipped': skipped, 'clipped': clipped, 'last_norm': float(f[1]), 'last_nonfinite': int(s[2]),
+                'mean_norm': float(f[6]) / max(steps - skipped, 1), 'max_norm_seen': float(f[7])}
+
+
 class Trainer(object):
-    def __init__(self, params, cfg=None, device='cuda', im_hw=(600, 1000), metrics=None):
-        """metrics: a metric.TrainMetrics (default None: no metric launch, no extra output).  With one, every step adds the reference's
+    def __init__(self, params, cfg=None, device='cuda', im_hw=(600, 1000), metrics=None, guard=None):
+        """guard: a GradGuard (default None: the optimizer applies whatever the gradient buffers hold); `tr.guard` may also be set or
+        cleared between updates.
+        metrics: a metric.TrainMetrics (default None: no metric launch, no extra output).  With one, every step adds the reference's
         training metrics into its device accumulator -- no host synchronisation, also inside a CapturedStep -- and `out` additionally carries
         rpn_cls_prob, rpn_label, cls_prob, nms_conditional_score and the loss tensors behind the loss scalars (rpn_bbox_loss_map, bbox_loss_map,
         nms_pos_loss_map, nms_neg_loss_map): the output list of the reference's train graph, which metric.py's host classes take."""
@@ -213,6 +273,7 @@ class Trainer(object):
         self.anchors_host = generate_anchors(c.feat_stride, c.anchor_ratios, c.anchor_scales)      # float64 [A,4], host (kernel argument)
         self.anchors = torch.as_tensor(self.anchors_host, dtype=torch.float64, device=dev)
         self.step_count = 0
+        self.guard = guard
         self.metrics = metrics
         if metrics is not None:         # which metrics exist follows the graph: RPN ones with an RPN in it, NMS ones with the learn-NMS head
             metrics.has_rpn, metrics.has_nms = not self.fpn, bool(c.learn_nms)
@@ -1072,19 +1133,36 @@ class Trainer(object):
             cache[key] = rs
         return cache[key]
 
-    def _sgd(self, buf, lo, hi, lr, wd, bf16=True):
+    def _sgd(self, buf, lo, hi, lr, wd, bf16=True, guard=None):
         for a, b_ in self._trainable_ranges(buf):          # (fixed parameters: neither gradient step nor weight decay nor momentum)
             l, h = max(lo, a), min(hi, b_)
-            if h > l:
+            if h > l and guard is None:
                 T.sgd_update(buf.master[l:h], buf.mom[l:h], buf.grad[l:h], lr, self.cfg.momentum, wd, 1.0,
                              w_bf16=buf.work[l:h] if bf16 else None)
+            elif h > l:
+                T.sgd_update_guarded(buf.master[l:h], buf.mom[l:h], buf.grad[l:h], lr, guard.state, self.cfg.momentum, wd, 1.0,
+                                     clip_gradient=-1.0 if guard.clip_gradient is None else guard.clip_gradient,
+                                     w_bf16=buf.work[l:h] if bf16 else None)
+
+    def _grad_views(self, buf, lo, hi):
+        """The trainable gradient ranges of a flat buffer inside [lo, hi): what `_sgd` updates there (frozen slices excluded, the
+        lr_mult tail included -- lr_mult scales the step, not the gradient)."""
+        return [buf.grad[max(lo, a):min(hi, b_)] for a, b_ in self._trainable_ranges(buf) if min(hi, b_) > max(lo, a)]
 
     def update(self, lr=None):
         """mx.optimizer.SGD over the flat buffers.  One rank (or everything already waited for): one launch for the weights, one for
-        the biases.  With bucket all-reduces in flight (all_reduce(wait=False)): per bucket, in launch order, wait + SGD on its slice."""
+        the biases.  With bucket all-reduces in flight (all_reduce(wait=False)): per bucket, in launch order, wait + SGD on its slice.
+
+        With a guard (`self.guard`, a GradGuard) the gradient statistics take SGD's place in that loop -- a bucket's are launched right
+        after its wait and run while later buckets are still in flight, the biases' after the bias wait -- then ONE decide launch, then
+        the guarded SGD launches.  The decision needs every gradient, so with a guard SGD starts only after the last collective has
+        landed: that is inherent in a global norm.  On one rank the guard adds three launches (statistics of the weights, of the
+        biases, decide; one more statistics launch per 16 trainable ranges of a buffer beyond the first 16).  `step_count` advances on
+        a skipped step too: the host does not know, and the LR schedule stays a function of the call count."""
         c = self.cfg
         lr = c.lr if lr is None else lr
         W, Bv = self.W, self.Bv
+        guard = self.guard
         wo, bo, mult = self.lr_mult_tail if self.lr_mult_tail is not None else (W.size, Bv.size, 1.0)
         bk = self._grad_buckets()
         pending = []
@@ -1101,6 +1179,11 @@ class Trainer(object):
         self.update_order = []                      # (bucket index, its collective had completed when SGD was queued) -- test hook
         ranges = [(self._bucket_cuts[i], self._bucket_cuts[i + 1], i) for i in pending] if pending else [(0, W.size, None)]
         timing = getattr(self, 'comm_timing', None)   # list (bench.py --gpus N): per bucket, (name, event before the wait, event after it)
+        if guard is not None:
+            guard.bind(W.grad.device)
+            plan = [self._grad_views(W, lo, hi) for lo, hi, _ in ranges] + [self._grad_views(Bv, 0, Bv.size)]
+            guard.begin(sum(T.grad_stats_slots([v.numel() for v in vs[k:k + T.GUARD_MAX_RANGES]])
+                            for vs in plan for k in range(0, len(vs), T.GUARD_MAX_RANGES)))
         for lo, hi, i in ranges:
             if i is not None:
                 self.update_order.append((i, bk.is_completed(i)))
@@ -1111,6 +1194,9 @@ class Trainer(object):
                 if timing is not None:
                     e1.record()
                     timing.append((self._bucket_names[i], e0, e1))
+            if guard is not None:
+                guard.stats(self._grad_views(W, lo, hi))
+                continue
             # parameters with lr_mult != 1 (DCN `offset` FC) sit at the tail of both flat buffers
             self._sgd(W, lo, min(hi, wo), lr, c.wd)
             self._sgd(W, max(lo, wo), hi, lr * mult, c.wd)
@@ -1125,8 +1211,14 @@ class Trainer(object):
                 e1.record()
                 timing.append(('biases', e0, e1))
             self._bias_work = None
-        self._sgd(Bv, 0, bo, lr, 0.0, bf16=False)
-        self._sgd(Bv, bo, Bv.size, lr * mult, 0.0, bf16=False)
+        if guard is not None:
+            guard.stats(self._grad_views(Bv, 0, Bv.size))
+            guard.decide()
+            for lo, hi, _ in ranges:
+                self._sgd(W, lo, min(hi, wo), lr, c.wd, guard=guard)
+                self._sgd(W, max(lo, wo), hi, lr * mult, c.wd, guard=guard)
+        self._sgd(Bv, 0, bo, lr, 0.0, bf16=False, guard=guard)
+        self._sgd(Bv, bo, Bv.size, lr * mult, 0.0, bf16=False, guard=guard)
         self.step_count += 1
 
     def comm_report(self, steps):
@@ -1245,10 +1337,10 @@ class FPNTrainer(Trainer):
 
     scales = (1 / 4.0, 1 / 8.0, 1 / 16.0, 1 / 32.0)
 
-    def __init__(self, params, cfg=None, device='cuda', metrics=None):
+    def __init__(self, params, cfg=None, device='cuda', metrics=None, guard=None):
         cfg = cfg or TrainConfig()
         cfg.fpn = True
-        Trainer.__init__(self, params, cfg, device, im_hw=None, metrics=metrics)
+        Trainer.__init__(self, params, cfg, device, im_hw=None, metrics=metrics, guard=guard)
 
     def _forward_backward_impl(self, data, im_info, gt_boxes, proposals, num_gt=None, num_proposals=None):
         """data [B,3,H,W] (H, W multiples of 32), proposals [B,N,4] fp32, gt_boxes [B,G,5]; num_proposals [B] int32

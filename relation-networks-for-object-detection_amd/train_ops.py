@@ -100,6 +100,73 @@ def sgd_update(w, mom, grad, lr, momentum=0.9, wd=0.0005, rescale_grad=1.0, w_bf
               float(momentum), float(wd), float(rescale_grad), _stream())
 
 
+GUARD_STATE_BYTES = 64        # relnet_grad_guard_state (include/relnet_hip.h)
+GUARD_SLOT_BYTES = 16         # one workgroup's partials: double sum of squares, int64 non-finite count
+GUARD_MAX_RANGES = 16         # ranges per relnet_grad_stats launch
+
+
+def grad_guard_state(device):
+    """A fresh relnet_grad_guard_state as 8 int64 words: all zero, scale = 1.0f.  Views: .view(torch.int32)[0] skip,
+    .view(torch.float32)[1] scale, .view(torch.float64)[1] last_norm, [2] last_nonfinite, [3:6] steps / skipped / clipped,
+    .view(torch.float64)[6:8] norm_sum / norm_max."""
+    st = torch.zeros(GUARD_STATE_BYTES // 8, device=device, dtype=torch.int64)
+    st.view(torch.float32)[1] = 1.0
+    return st
+
+
+def grad_guard_workspace(slots, device):
+    """Workspace of `slots` statistics slots (int64 words; needs no initialisation: every slot that is read was written first)."""
+    nbytes = _lib.load().relnet_grad_guard_workspace_bytes(int(slots))
+    assert nbytes == slots * GUARD_SLOT_BYTES
+    return torch.empty(nbytes // 8, device=device, dtype=torch.int64)
+
+
+def grad_stats_slots(ns):
+    """Slots (= workgroups) one relnet_grad_stats launch over ranges of ns[i] elements writes.  Host only."""
+    import ctypes as C
+    n = len(ns)
+    r = _lib.load().relnet_grad_stats_slots((C.c_long * n)(*[int(v) for v in ns]), n)
+    if r < 0:
+        raise _lib.RelnetError("relnet_grad_stats_slots: 1..%d ranges of >= 1 element, got %s" % (GUARD_MAX_RANGES, list(ns)))
+    return r
+
+
+def grad_stats(views, workspace, slot_base=0):
+    """Sum of squares and non-finite count of up to 16 fp32 ranges (1-D contiguous views) in one launch: slot slot_base + b of `workspace`
+    receives workgroup b's partials.  Returns the number of slots written."""
+    import ctypes as C
+    _chk(workspace, *views)
+    n = len(views)
+    for v in views:
+        assert v.dtype == torch.float32 and v.is_contiguous() and v.numel() > 0
+    assert workspace.dtype == torch.int64 and workspace.is_contiguous()
+    ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in views])
+    ns = (C.c_long * n)(*[v.numel() for v in views])
+    _lib.call('relnet_grad_stats', ptrs, ns, n, workspace.data_ptr(), int(slot_base), workspace.numel() * 8 // GUARD_SLOT_BYTES, _stream())
+    return grad_stats_slots([v.numel() for v in views])
+
+
+def grad_guard_decide(workspace, n_slots, state, max_norm=0.0):
+    """Fold slots [0, n_slots) and update the guard state (skip, scale, last norm / count, totals).  max_norm <= 0: no global-norm clipping."""
+    _chk(workspace, state)
+    assert state.dtype == torch.int64 and state.numel() * 8 == GUARD_STATE_BYTES and state.is_contiguous()
+    assert workspace.dtype == torch.int64 and 0 < n_slots * GUARD_SLOT_BYTES <= workspace.numel() * 8
+    _lib.call('relnet_grad_guard_decide', workspace.data_ptr(), int(n_slots), float(max_norm), state.data_ptr(), _stream())
+
+
+def sgd_update_guarded(w, mom, grad, lr, state, momentum=0.9, wd=0.0005, rescale_grad=1.0, clip_gradient=-1.0, w_bf16=None):
+    """sgd_update under a guard state: nothing is written when state.skip is set, otherwise the gradient term is
+    clip((rescale_grad * grad) * state.scale, +-clip_gradient) (clip_gradient < 0: off).  skip / scale are read on the device."""
+    _chk(w, mom, grad, w_bf16, state)
+    assert w.dtype == torch.float32 and mom.dtype == torch.float32 and grad.dtype == torch.float32
+    assert w.is_contiguous() and mom.is_contiguous() and grad.is_contiguous() and grad.numel() == w.numel() == mom.numel()
+    assert state.dtype == torch.int64 and state.numel() * 8 == GUARD_STATE_BYTES
+    if w_bf16 is not None:
+        assert w_bf16.dtype == torch.bfloat16 and w_bf16.is_contiguous() and w_bf16.numel() == w.numel()
+    _lib.call('relnet_sgd_update_guarded', w.data_ptr(), mom.data_ptr(), grad.data_ptr(), _ptr(w_bf16), w.numel(), float(lr),
+              float(momentum), float(wd), float(rescale_grad), state.data_ptr(), float(clip_gradient), _stream())
+
+
 def _splits_for(m, n, k):
     """split-K factor of a weight-gradient GEMM [m, n] with a long contraction k: enough tiles to fill 256 CUs."""
     tiles = ((m + 255) // 256) * ((n + 255) // 256)
