@@ -813,6 +813,51 @@ int relnet_metric_sum_count(const float* x, const float* x2, long n, const float
                             double* sum, double* sum2, long long* count, void* workspace, void* stream);
 int relnet_metric_nms_acc(const float* target, const float* cond, long n, long long* counts, void* stream);
 
+/* ---- Deterministic training mode (train.TrainConfig.deterministic) -----------------------------------------
+ * Ordered forms of the float accumulations of a training step whose order the atomic forms leave to the hardware: no float atomic,
+ * global or LDS, the same bits on every run.  The entry points they stand in for keep their signatures and their behaviour.
+ * relnet_roi_pool_bwd_ordered (for relnet_roi_pool_bwd_ex / relnet_roi_pool_bwd_cl): grad_in element (b, c, cell) at b gs_b + c gs_c +
+ *   cell gs_p is WRITTEN with the fp32 sum, starting from 0, of grad_out[r][c][ph][pw] over the bins of image b's rois whose argmax is the
+ *   cell, in ascending (roi, ph, pw) order (gather form: one thread per (image, cell, channel | 8 bf16 channels); no zero fill needed).
+ *   spatial_scale, H and W are the forward's; single map only (no FPN level table).
+ * relnet_colsum_add_ordered / relnet_colsum_add_grouped_ordered (for relnet_colsum_add / relnet_colsum_add_grouped): out[c] += the column
+ *   sum, in two launches: row chunk k = rows [k rpb, (k + 1) rpb) with nchunk = min(128, ceil(rows / 512)), rpb = ceil(rows / nchunk);
+ *   inside a chunk row lane l < 8 sums rows r0 + l, r0 + l + 8, ... ascending from 0, the partial is the ascending sum of the 8 lanes
+ *   from 0, and out[c] += the ascending sum of the partials from 0.  The tree depends on (rows, cols, dtype) only: not on the CU count,
+ *   not on alignment (the 16-byte bf16 path walks the same tree), not on the group a problem rides in.  Any dtype per problem (dtypes[i]);
+ *   the outputs of one group must not overlap (checked).  workspace: 16-byte aligned, at least the sum of
+ *   relnet_colsum_ordered_workspace_bytes(rows[i], cols[i]); it needs no initialisation and is free again when the launches have run.
+ * relnet_reduce_scalar_ordered (for relnet_reduce_scalar): min(64, ceil(n / 4096)) scaled workgroup sums into the workspace
+ *   (relnet_reduce_scalar_workspace_bytes()), then out[0] = their ascending sum.
+ * relnet_geometry_bias_bwd_ordered (for relnet_geometry_bias_bwd): the same kernels write per-slot partial sums (slot = (image, query)
+ *   for the per-wavefront kernels, = workgroup for the matrix-core kernel, whose grid is min(768, ceil(B N / 4))) into the workspace
+ *   (relnet_geometry_bias_bwd_workspace_bytes(B, N)); a second launch adds them to dwp / dbp: per word, lane l < 16 sums slots l, l + 16, ..
+ *   ascending from 0, then the 16 lanes ascending from 0.
+ * relnet_lnms_take_bwd_ordered (for the index_add_ scatter of the learn-NMS branch, and relnet_lnms_take_bwd's operand limits):
+ *   d_emb fp32 [B N][128], every row WRITTEN with the fp32 sum from 0 of the rows of d_x [B][C][F][128] (dtype 0 fp32 / 1 bf16) whose
+ *   rank_idx [B][C][F] names the roi, in ascending flat source index (b C + c) F + f.  Ranks of one (image, class) must be distinct
+ *   (they are a prefix of a sorted permutation); negative ranks are skipped; any C.
+ * relnet_wgrad_grouped_ex (for relnet_wgrad_grouped + relnet_wgrad_tune's workgroup count): workgroups = the launch's persistent grid
+ *   (0 = default) as an argument; deterministic != 0 = whole-tile shares (one workgroup owns an output tile, pixel slabs in ascending
+ *   order, plain read-modify-write) and no fall-back to atomics: layers whose gradient ranges overlap are split into consecutive
+ *   launches with disjoint writers, in queue order. */
+int relnet_roi_pool_bwd_ordered(const void* grad_out, const int* argmax, const long* out_strides4, const float* rois, float* grad_in,
+                                long gs_b, long gs_c, long gs_p, int B, int H, int W, int R, int C, int PH, int PW, float spatial_scale,
+                                int batch_index_base, int dtype, void* stream);
+long relnet_colsum_ordered_workspace_bytes(long rows, int cols);
+int relnet_colsum_add_ordered(const void* x, long ld, long rows, int cols, int dtype, float* out, void* workspace, long workspace_bytes,
+                              void* stream);
+int relnet_colsum_add_grouped_ordered(const void* const* xs, const long* lds, const long* rows, const int* cols, const int* dtypes,
+                                      float* const* outs, int n, void* workspace, long workspace_bytes, void* stream);
+long relnet_reduce_scalar_workspace_bytes(void);
+int relnet_reduce_scalar_ordered(const float* x, long n, float scale, int mode, float* out, void* workspace, void* stream);
+long relnet_geometry_bias_bwd_workspace_bytes(int B, int N);
+int relnet_geometry_bias_bwd_ordered(const float* boxes, int box_stride, int box_off, const float* bias, const float* dlog,
+                                     const float* divisors8, float* dwp, float* dbp, int B, int N, int M, int Mpad, int fast_math,
+                                     void* workspace, long workspace_bytes, void* stream);
+int relnet_lnms_take_bwd_ordered(const void* d_x, const int* rank_idx, float* d_emb, int B, int N, int C, int F, int dtype, void* stream);
+int relnet_wgrad_grouped_ex(const relnet_wgrad_desc* descs, int n, void* table_workspace, int workgroups, int deterministic, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,53 @@ __global__ __launch_bounds__(256) void lnms_take_bwd_gather_kernel(const unsigne
   *(uint4*)(d_emb + ((long)b * N + n) * 128 + col) = make_uint4(pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]), pack_bf16x2(acc[4], acc[5]), pack_bf16x2(acc[6], acc[7]));
 }
 
+// Ordered take adjoint for every operand the gather above does not cover (deterministic training mode; replaces the index_add_ scatter of that branch):
+// d_emb[b N + n][:] (fp32, written once) = the fp32 sum, starting from 0, of d_x[b][c][p][:] over the (c, p) with rank_idx[b][c][p] == n, taken in
+// ascending flat source index (b C + c) F + p.  The ranks of one (image, class) are distinct (a prefix of the class's argsort), so a roi has at most one
+// position per class and ascending class IS ascending flat index; the classes are walked in chunks of 128 through the same LDS position table.
+template <typename T>
+__global__ __launch_bounds__(256) void lnms_take_bwd_ordered_kernel(const T* d_x, const int* rank_idx, float* d_emb, int N, int C, int F) {
+  __shared__ short pos[128 * 16];                 // [class of the chunk][16]
+  const int chunks = (N + 15) / 16;
+  const int b = blockIdx.x / chunks, n0 = (blockIdx.x % chunks) * 16;
+  const int r = threadIdx.x >> 4, col = (threadIdx.x & 15) * 8;       // 16 rois x 16 column groups of 8
+  const int n = n0 + r;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int cb = 0; cb < C; cb += 128) {
+    const int cn = min(128, C - cb);
+    for (int i = threadIdx.x; i < cn * 16; i += 256) pos[i] = -1;
+    __syncthreads();
+    const int* rk = rank_idx + ((long)b * C + cb) * F;
+    for (int i = threadIdx.x; i < cn * F; i += 256) {
+      const int q = rk[i] - n0;
+      if (q >= 0 && q < 16) pos[(i / F) * 16 + q] = (short)(i % F);
+    }
+    __syncthreads();
+    if (n < N) {
+      const T* base = d_x + ((long)b * C + cb) * F * 128 + col;
+      for (int c = 0; c < cn; ++c) {
+        const int p = pos[c * 16 + r];
+        if (p < 0) continue;
+        const T* src = base + ((long)c * F + p) * 128;
+        if constexpr (sizeof(T) == 2) {
+          const uint4 v = *(const uint4*)src;
+          const unsigned int u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { acc[2 * e] += __uint_as_float(u[e] << 16); acc[2 * e + 1] += __uint_as_float(u[e] & 0xffff0000u); }
+        } else {
+          const float4 v0 = *(const float4*)src, v1 = *(const float4*)(src + 4);
+          acc[0] += v0.x; acc[1] += v0.y; acc[2] += v0.z; acc[3] += v0.w; acc[4] += v1.x; acc[5] += v1.y; acc[6] += v1.z; acc[7] += v1.w;
+        }
+      }
+    }
+    __syncthreads();                              // the table is rebuilt for the next chunk of classes
+  }
+  if (n >= N) return;
+  float* dst = d_emb + ((long)b * N + n) * 128 + col;
+  *(float4*)dst = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  *(float4*)(dst + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+}
+
 // one wavefront per (b, n): prob = softmax(cls_score)[1:], so with inner = sum_c prob_c d_prob_c and p_bg = 1 - sum_c prob_c:
 //   d cls_score[0] += -p_bg inner;   d cls_score[1 + c] += prob_c (d_prob_c - inner)
 __global__ __launch_bounds__(256) void lnms_softmax_bwd_kernel(const float* prob, const float* d_prob, float* d_cls, long ld_row, long ld_img,
@@ -221,6 +268,18 @@ extern "C" int relnet_lnms_take_bwd(const void* d_x, const int* rank_idx, void* 
   RELNET_REQUIRE((((uintptr_t)d_x | (uintptr_t)d_emb) & 15) == 0, "relnet_lnms_take_bwd: operands must be 16-byte aligned");
   lnms_take_bwd_gather_kernel<<<(unsigned)(B * ((N + 15) / 16)), 256, 0, (hipStream_t)stream>>>((const unsigned short*)d_x, rank_idx, (unsigned short*)d_emb, N, C, F);
   return check_launch("relnet_lnms_take_bwd");
+}
+
+// d_x [B][C][F][128] bf16 (dtype 1) or fp32 (dtype 0), rank_idx [B][C][F] (negative = padding, skipped; distinct within one (image, class)),
+// d_emb [B N][128] fp32, every row written.  See lnms_take_bwd_ordered_kernel for the defined order.
+extern "C" int relnet_lnms_take_bwd_ordered(const void* d_x, const int* rank_idx, float* d_emb, int B, int N, int C, int F, int dtype, void* stream) {
+  RELNET_REQUIRE(d_x && rank_idx && d_emb && B > 0 && N > 0 && C > 0 && F > 0 && F < 32768, "relnet_lnms_take_bwd_ordered: bad arguments");
+  RELNET_REQUIRE(dtype == 0 || dtype == 1, "relnet_lnms_take_bwd_ordered: unknown dtype %d", dtype);
+  RELNET_REQUIRE((((uintptr_t)d_x | (uintptr_t)d_emb) & 15) == 0, "relnet_lnms_take_bwd_ordered: operands must be 16-byte aligned");
+  const unsigned grid = (unsigned)(B * ((N + 15) / 16));
+  if (dtype == 1) lnms_take_bwd_ordered_kernel<unsigned short><<<grid, 256, 0, (hipStream_t)stream>>>((const unsigned short*)d_x, rank_idx, d_emb, N, C, F);
+  else lnms_take_bwd_ordered_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)d_x, rank_idx, d_emb, N, C, F);
+  return check_launch("relnet_lnms_take_bwd_ordered");
 }
 
 extern "C" int relnet_lnms_softmax_bwd(const float* prob, const float* d_prob, float* d_cls, long ld_row, long ld_img, int B, int N, int C, void* stream) {

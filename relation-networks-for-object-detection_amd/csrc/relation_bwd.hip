@@ -608,7 +608,9 @@ struct GeomBwdArgs {
   float* dwp;                                     // [16][64] (+=, atomics)
   float* dbp;                                     // [16]     (+=, atomics)
   int B, N, M, Mpad;
+  float* part;                                    // ordered form: [slots][kGeomPartWords] per-wavefront / per-workgroup partial sums instead of the atomics (nullptr: atomics)
 };
+constexpr int kGeomPartWords = 16 * 64 + 16;      // one slot: dwp [16][64], then dbp [16]
 
 #pragma clang fp contract(off)
 __device__ __forceinline__ float position_feature_1(float4 bi, float4 bj, int comp) {
@@ -696,13 +698,24 @@ __global__ __launch_bounds__(256) void geometry_bias_bwd_kernel(GeomBwdArgs g) {
     }
   }
   // rows h = (r & 3) + 8 (r >> 2) + 4 half < 16  <=>  r < 8 ; col = l31
+  bsum += __shfl_xor(bsum, 32);
+  if (g.part) {                                  // ordered form: slot = (image, query); every slot of the B N is written by exactly this wavefront
+    float* slot = g.part + ((long)b * g.N + i) * kGeomPartWords;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int hrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+      slot[hrow * 64 + l31] = c0[r];
+      slot[hrow * 64 + 32 + l31] = c1[r];
+    }
+    if (lane < 16) slot[16 * 64 + lane] = bsum;
+    return;
+  }
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const int hrow = (r & 3) + 8 * (r >> 2) + 4 * half;
     atomicAdd(g.dwp + hrow * 64 + l31, c0[r]);
     atomicAdd(g.dwp + hrow * 64 + 32 + l31, c1[r]);
   }
-  bsum += __shfl_xor(bsum, 32);
   if (lane < 16) atomicAdd(g.dbp + lane, bsum);
 }
 
@@ -803,11 +816,38 @@ __global__ __launch_bounds__(256) void geometry_bias_bwd_mfma_kernel(GeomBwdArgs
       float v0 = c0[r], v1 = c1[r];
 #pragma unroll
       for (int w = 0; w < 3; ++w) { v0 += sRed[w][hrow][l31]; v1 += sRed[w][hrow][32 + l31]; }
-      atomicAdd(g.dwp + hrow * 64 + l31, v0);
-      atomicAdd(g.dwp + hrow * 64 + 32 + l31, v1);
+      if (g.part) {                              // ordered form: slot = workgroup (the grid is a function of B N alone)
+        g.part[(long)blockIdx.x * kGeomPartWords + hrow * 64 + l31] = v0;
+        g.part[(long)blockIdx.x * kGeomPartWords + hrow * 64 + 32 + l31] = v1;
+      } else {
+        atomicAdd(g.dwp + hrow * 64 + l31, v0);
+        atomicAdd(g.dwp + hrow * 64 + 32 + l31, v1);
+      }
     }
-    if (lane < 16) atomicAdd(g.dbp + lane, bsum + sB[0][lane] + sB[1][lane] + sB[2][lane]);
+    const float bt = bsum + sB[0][lane & 15] + sB[1][lane & 15] + sB[2][lane & 15];
+    if (lane < 16) {
+      if (g.part) g.part[(long)blockIdx.x * kGeomPartWords + 16 * 64 + lane] = bt;
+      else atomicAdd(g.dbp + lane, bt);
+    }
   }
+}
+
+// ordered form, second stage: workgroup = 16 of the 1040 words x 16 slot lanes.  Lane l adds slots l, l + 16, ... ascending from 0; the word's total is
+// the ascending sum of the 16 lanes from 0; dwp / dbp += that.  (First form: one thread per word walking every slot -- 5 workgroups, 155 us at 768 slots.)
+__global__ __launch_bounds__(256) void geometry_bias_bwd_fold_kernel(const float* part, int slots, float* dwp, float* dbp) {
+  __shared__ float lanes[16][17];
+  const int w = threadIdx.x & 15, l = threadIdx.x >> 4;
+  const int o = blockIdx.x * 16 + w;                 // (1040 = 65 x 16: every workgroup is full)
+  float t = 0.f;
+  for (int k = l; k < slots; k += 16) t += part[(long)k * kGeomPartWords + o];
+  lanes[l][w] = t;
+  __syncthreads();
+  if (l != 0) return;
+  float total = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) total += lanes[q][w];
+  if (o < 16 * 64) dwp[o] += total;
+  else dbp[o - 16 * 64] += total;
 }
 
 }  // namespace relnet
@@ -902,21 +942,47 @@ extern "C" int relnet_relation_attention_bwd(
                                           B, H, N, M, Mpad, Npad, scale, dtype, nullptr, stream);
 }
 
+// part == nullptr: the atomic form.  Otherwise the ordered form: per-slot partial sums into `part` (>= relnet_geometry_bias_bwd_workspace_bytes(B, N)
+// bytes), then geometry_bias_bwd_fold_kernel adds them to dwp / dbp in a fixed order.
+static int geometry_bias_bwd_launch(const float* boxes, int box_stride, int box_off, const float* bias, const float* dlog, const float* divisors8,
+                                    float* dwp, float* dbp, int B, int N, int M, int Mpad, int fast_math, float* part, void* stream, const char* what) {
+  GeomBwdArgs g;
+  g.boxes = boxes; g.box_stride = box_stride; g.box_off = box_off; g.bias = bias; g.dlog = dlog;
+  for (int k = 0; k < 8; ++k) g.divisors[k] = divisors8[k];
+  g.dwp = dwp; g.dbp = dbp; g.B = B; g.N = N; g.M = M; g.Mpad = Mpad; g.part = part;
+  dim3 grid((unsigned)((N + 3) / 4), B);
+  long slots = (long)B * N;                       // the per-wavefront kernels: one slot per (image, query)
+  if (fast_math == 1 && Mpad % 32 == 0 && (((uintptr_t)bias | (uintptr_t)dlog) & 15) == 0) {
+    const long total_q = (long)B * N;             // grid-stride over the (image, query) rows: <= 768 workgroups
+    const long blocks = (total_q + 3) / 4;
+    slots = blocks < 768 ? blocks : 768;
+    geometry_bias_bwd_mfma_kernel<<<(unsigned)slots, 256, 0, (hipStream_t)stream>>>(g, (int)total_q);
+  } else if (fast_math) geometry_bias_bwd_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(g);
+  else geometry_bias_bwd_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(g);
+  if (part) geometry_bias_bwd_fold_kernel<<<kGeomPartWords / 16, 256, 0, (hipStream_t)stream>>>(part, (int)slots, dwp, dbp);
+  return check_launch(what);
+}
+
 extern "C" int relnet_geometry_bias_bwd(const float* boxes, int box_stride, int box_off, const float* bias,
                                         const float* dlog, const float* divisors8, float* dwp, float* dbp, int B,
                                         int N, int M, int Mpad, int fast_math, void* stream) {
   RELNET_REQUIRE(boxes && bias && dlog && divisors8 && dwp && dbp, "relnet_geometry_bias_bwd: null operand");
   RELNET_REQUIRE(B > 0 && N > 0 && M > 0 && Mpad >= M, "relnet_geometry_bias_bwd: bad shape");
-  GeomBwdArgs g;
-  g.boxes = boxes; g.box_stride = box_stride; g.box_off = box_off; g.bias = bias; g.dlog = dlog;
-  for (int k = 0; k < 8; ++k) g.divisors[k] = divisors8[k];
-  g.dwp = dwp; g.dbp = dbp; g.B = B; g.N = N; g.M = M; g.Mpad = Mpad;
-  dim3 grid((unsigned)((N + 3) / 4), B);
-  if (fast_math == 1 && Mpad % 32 == 0 && (((uintptr_t)bias | (uintptr_t)dlog) & 15) == 0) {
-    const long total_q = (long)B * N;             // grid-stride over the (image, query) rows: <= 768 workgroups
-    const long blocks = (total_q + 3) / 4;
-    geometry_bias_bwd_mfma_kernel<<<(unsigned)(blocks < 768 ? blocks : 768), 256, 0, (hipStream_t)stream>>>(g, (int)total_q);
-  } else if (fast_math) geometry_bias_bwd_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(g);
-  else geometry_bias_bwd_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(g);
-  return check_launch("relnet_geometry_bias_bwd");
+  return geometry_bias_bwd_launch(boxes, box_stride, box_off, bias, dlog, divisors8, dwp, dbp, B, N, M, Mpad, fast_math, nullptr, stream,
+                                  "relnet_geometry_bias_bwd");
+}
+
+extern "C" long relnet_geometry_bias_bwd_workspace_bytes(int B, int N) {
+  return B > 0 && N > 0 ? (long)B * N * kGeomPartWords * (long)sizeof(float) : 0;
+}
+
+extern "C" int relnet_geometry_bias_bwd_ordered(const float* boxes, int box_stride, int box_off, const float* bias,
+                                                const float* dlog, const float* divisors8, float* dwp, float* dbp, int B,
+                                                int N, int M, int Mpad, int fast_math, void* workspace, long workspace_bytes, void* stream) {
+  RELNET_REQUIRE(boxes && bias && dlog && divisors8 && dwp && dbp && workspace, "relnet_geometry_bias_bwd_ordered: null operand");
+  RELNET_REQUIRE(B > 0 && N > 0 && M > 0 && Mpad >= M, "relnet_geometry_bias_bwd_ordered: bad shape");
+  RELNET_REQUIRE(workspace_bytes >= relnet_geometry_bias_bwd_workspace_bytes(B, N), "relnet_geometry_bias_bwd_ordered: the workspace holds %ld bytes, B = %d, N = %d need %ld",
+                 workspace_bytes, B, N, relnet_geometry_bias_bwd_workspace_bytes(B, N));
+  return geometry_bias_bwd_launch(boxes, box_stride, box_off, bias, dlog, divisors8, dwp, dbp, B, N, M, Mpad, fast_math, (float*)workspace, stream,
+                                  "relnet_geometry_bias_bwd_ordered");
 }

@@ -153,6 +153,90 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_kernel(RoiBwdArgs g) {
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Ordered backward (deterministic training mode): the GATHER form.  The value of every gradient word is DEFINED as the fp32 sum, starting from
+// 0, of grad_out[r][c][ph][pw] over the bins whose argmax is that cell, taken in ascending (roi, ph, pw) order -- no atomics, global or LDS, and
+// the word is written once (grad_in needs no zero fill).  One thread per (image, cell, channel | 8-channel vector) walks the rois in ascending
+// index; from the roi's geometry it derives the bins that can contain the cell (the forward's own window arithmetic on a range one bin wider
+// than the real-number solution, so that a product the forward rounded across an integer is still inside) and adds where argmax == cell.  The
+// argmax test decides: a candidate bin that does not hold the cell only costs its load.
+// ---------------------------------------------------------------------------------------
+struct RoiBwdOrdArgs {
+  const void* grad_out; const int* argmax; long os_r, os_c, os_ph, os_pw;
+  const float* rois;
+  float* grad_in; long ds_b, ds_c, ds_p;
+  int R, C, H, W, PH, PW, batch_index_base;
+  float scale;
+};
+
+#pragma clang fp contract(off)
+// candidate bins [lo, hi] along one axis for cell coordinate y of a roi that starts at cell rs and spans rn cells: bin p covers
+// [floor(p bin), ceil((p + 1) bin)) + rs  =>  y - rs + 1 > p bin  and  (p + 1) bin > y - rs; one extra bin on either side
+__device__ __forceinline__ bool roi_bin_range(int y, int rs, int rn, int P, float bin, int& lo, int& hi) {
+  const int rel = y - rs;
+  if (rel < -1 || rel > rn + 1) return false;
+  lo = max((int)floorf((float)rel / bin) - 1, 0);
+  hi = min((int)ceilf((float)(rel + 1) / bin), P - 1);
+  return lo <= hi;
+}
+// does bin p of that axis hold cell y?  (roi_pool_fwd_kernel's arithmetic, L = the map's extent)
+__device__ __forceinline__ bool roi_bin_holds(int p, int y, int rs, float bin, int L) {
+  const int s = min(max((int)floorf((float)p * bin) + rs, 0), L), e = min(max((int)ceilf((float)(p + 1) * bin) + rs, 0), L);
+  return y >= s && y < e;
+}
+
+// VEC = 1: thread = (cell, channel), any strides.  VEC = 8: thread = (cell, 8 channels), bf16 grad_out with os_c == 1, ds_c == 1 and 16-byte aligned rows.
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void roi_pool_bwd_ordered_kernel(RoiBwdOrdArgs g) {
+  const int b = blockIdx.y;
+  const int cv = g.C / VEC;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)g.H * g.W * cv) return;
+  const int c0 = (int)(t % cv) * VEC, cell = (int)(t / cv);
+  const int y = cell / g.W, x = cell - y * g.W;
+  float acc[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+  for (int r = 0; r < g.R; ++r) {
+    const float* roi = g.rois + (long)r * 5;
+    if ((int)roi[0] - g.batch_index_base != b) continue;
+    const int rs_w = (int)roundf(roi[1] * g.scale), rs_h = (int)roundf(roi[2] * g.scale);
+    const int re_w = (int)roundf(roi[3] * g.scale), re_h = (int)roundf(roi[4] * g.scale);
+    const int rw = max(re_w - rs_w + 1, 1), rh = max(re_h - rs_h + 1, 1);
+    const float bin_h = (float)rh / (float)g.PH, bin_w = (float)rw / (float)g.PW;
+    int ph0, ph1, pw0, pw1;
+    if (!roi_bin_range(y, rs_h, rh, g.PH, bin_h, ph0, ph1) || !roi_bin_range(x, rs_w, rw, g.PW, bin_w, pw0, pw1)) continue;
+    for (int ph = ph0; ph <= ph1; ++ph) {
+      if (!roi_bin_holds(ph, y, rs_h, bin_h, g.H)) continue;
+      for (int pw = pw0; pw <= pw1; ++pw) {
+        if (!roi_bin_holds(pw, x, rs_w, bin_w, g.W)) continue;
+        const long o = (long)r * g.os_r + (long)c0 * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw;
+        if constexpr (VEC == 8) {
+          const int4 a0 = *(const int4*)(g.argmax + o), a1 = *(const int4*)(g.argmax + o + 4);
+          const int a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+          const uint4 w = *(const uint4*)((const unsigned short*)g.grad_out + o);
+          const unsigned int w4[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (a[2 * e] == cell) acc[2 * e] += bf2f(w4[e] & 0xffff);
+            if (a[2 * e + 1] == cell) acc[2 * e + 1] += bf2f(w4[e] >> 16);
+          }
+        } else {
+          if (g.argmax[o] == cell) acc[0] += ld<T>((const T*)g.grad_out + o);
+        }
+      }
+    }
+  }
+  float* dst = g.grad_in + (long)b * g.ds_b + (long)c0 * g.ds_c + (long)cell * g.ds_p;
+  if constexpr (VEC == 8) {
+    *(float4*)dst = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    *(float4*)(dst + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+  } else {
+    *dst = acc[0];
+  }
+}
+#pragma clang fp contract(fast)
+
 }  // namespace relnet
 
 using namespace relnet;
@@ -345,6 +429,29 @@ extern "C" int relnet_roi_pool_bwd_cl(const void* grad_out, const int* argmax, c
   if (dtype == RELNET_F32) roi_pool_bwd_kernel<float><<<grid, 256, 0, s>>>(g);
   else roi_pool_bwd_kernel<unsigned short><<<grid, 256, 0, s>>>(g);
   return check_launch("relnet_roi_pool_bwd_cl");
+}
+
+// Ordered form of relnet_roi_pool_bwd_ex / relnet_roi_pool_bwd_cl (see roi_pool_bwd_ordered_kernel): grad_in element (b, c, cell) at
+// b gs_b + c gs_c + cell gs_p is WRITTEN (not accumulated) for every b < B, c < C, cell < H W.  spatial_scale, H and W are the forward's.
+extern "C" int relnet_roi_pool_bwd_ordered(const void* grad_out, const int* argmax, const long* out_strides4, const float* rois, float* grad_in,
+                                           long gs_b, long gs_c, long gs_p, int B, int H, int W, int R, int C, int PH, int PW,
+                                           float spatial_scale, int batch_index_base, int dtype, void* stream) {
+  RELNET_REQUIRE(grad_out && argmax && out_strides4 && rois && grad_in, "relnet_roi_pool_bwd_ordered: null operand");
+  RELNET_REQUIRE(B > 0 && H > 0 && W > 0 && R > 0 && C > 0 && PH > 0 && PW > 0, "relnet_roi_pool_bwd_ordered: bad shape");
+  RELNET_REQUIRE(dtype == RELNET_F32 || dtype == RELNET_BF16, "relnet_roi_pool_bwd_ordered: unknown dtype %d", dtype);
+  RELNET_REQUIRE(B <= 65535, "relnet_roi_pool_bwd_ordered: at most 65535 images, got %d", B);
+  RoiBwdOrdArgs g{grad_out, argmax, out_strides4[0], out_strides4[1], out_strides4[2], out_strides4[3], rois, grad_in, gs_b, gs_c, gs_p,
+                  R, C, H, W, PH, PW, batch_index_base, spatial_scale};
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = dtype == RELNET_BF16 && C % 8 == 0 && g.os_c == 1 && gs_c == 1 && g.os_r % 8 == 0 && g.os_ph % 8 == 0 && g.os_pw % 8 == 0 &&
+                   gs_b % 4 == 0 && gs_p % 4 == 0 && (((uintptr_t)grad_out | (uintptr_t)argmax | (uintptr_t)grad_in) & 15) == 0;
+  const long threads = (long)H * W * (vec ? C / 8 : C);
+  RELNET_REQUIRE((threads + 255) / 256 < (1L << 31), "relnet_roi_pool_bwd_ordered: map too large");
+  dim3 grid((unsigned)((threads + 255) / 256), (unsigned)B);
+  if (vec) roi_pool_bwd_ordered_kernel<unsigned short, 8><<<grid, 256, 0, s>>>(g);
+  else if (dtype == RELNET_F32) roi_pool_bwd_ordered_kernel<float, 1><<<grid, 256, 0, s>>>(g);
+  else roi_pool_bwd_ordered_kernel<unsigned short, 1><<<grid, 256, 0, s>>>(g);
+  return check_launch("relnet_roi_pool_bwd_ordered");
 }
 
 extern "C" int relnet_roi_pool_bwd_ex(const void* grad_out, const int* argmax, const long* out_strides4,

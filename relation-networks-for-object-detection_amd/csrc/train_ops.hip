@@ -302,6 +302,9 @@ __global__ __launch_bounds__(256) void lnms_scatter_bwd_kernel(const float* d_so
   const long b = i / ((long)F * C);
   const int r = rank_idx[i];
   if (r < 0 || r >= N) return;
+  // (order: the ranks of one (image, class) are distinct roi indices -- lnms_sort_kernel writes the first F entries of a sorted permutation whose keys
+  //  carry the index -- so within a launch every (b, r, c) word has at most ONE contribution, added to the caller's zero: nothing for an order to decide,
+  //  the deterministic training mode keeps this kernel)
   atomicAdd(d_prob + (b * N + r) * C + c, d_sorted[(b * F + f) * C + c]);
 }
 
@@ -321,6 +324,108 @@ __global__ __launch_bounds__(256) void reduce_scalar_kernel(const float* x, long
   if (threadIdx.x == 0) atomicAdd(out, (mode ? 1.f : scale) * (part[0] + part[1] + part[2] + part[3]));
 }
 
+
+// ---------------------------------------------------------------------------------------
+// Ordered forms (deterministic training mode): the same sums as the kernels above without a float atomic, so that a rerun gives the
+// same bits.  Two stages -- per-block partial sums into a workspace, then a fixed-order final sum that adds into the output -- and
+// the partition and the tree are functions of (rows, cols, dtype) alone, never of the CU count, a knob or the launch a sum rides in:
+//   chunk k      = rows [k rpb, min((k + 1) rpb, rows)),  nchunk = min(128, ceil(rows / 512)),  rpb = ceil(rows / nchunk)
+//   row lane l   = fp32 sum from 0 of rows r0 + l, r0 + l + 8, ... of the chunk (l < 8), ascending
+//   partial k    = ((((((((0 + lane 0) + lane 1) + ...) + lane 7)
+//   out[c]      += (((0 + partial 0) + partial 1) + ...)  ascending k
+// The scalar and the 16-byte bf16 body walk the same tree (bf16 -> fp32 is exact), so alignment does not change a bit either.
+// ---------------------------------------------------------------------------------------
+struct OrdColsumProblem {
+  const void* x; float* out; float* part;            // part: [chunks][cols] fp32 in the workspace
+  long ld, rows, rows_per_block;
+  int cols, chunks, kind;                            // kind 0 = fp32, 1 = bf16, 2 = bf16 with 16-byte loads (8 | cols, 8 | ld, aligned)
+  int col_blocks, blk_start, blk2_start;             // stage-1 blocks per chunk / first block; first stage-2 block (256 columns each)
+};
+struct OrdColsumGroup { OrdColsumProblem p[16]; int n; };
+
+__global__ __launch_bounds__(256) void colsum_ordered_partial_kernel(OrdColsumGroup g) {
+  __shared__ float part[8][32][9];
+  int pi = 0;
+  for (int i = 1; i < g.n; ++i) if ((int)blockIdx.x >= g.p[i].blk_start) pi = i;
+  const OrdColsumProblem& a = g.p[pi];
+  const int rel = blockIdx.x - a.blk_start;
+  const int bx = rel % a.col_blocks, by = rel / a.col_blocks;
+  const int gq = threadIdx.x & 31, rl = threadIdx.x >> 5;
+  const long r0 = (long)by * a.rows_per_block, r1 = min(r0 + a.rows_per_block, a.rows);
+  if (a.kind == 2) {
+    const int c = (bx * 32 + gq) * 8;
+    const unsigned short* x = (const unsigned short*)a.x;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c < a.cols) {
+      for (long r = r0 + rl; r < r1; r += 8) {
+        const uint4 v = *(const uint4*)(x + r * a.ld + c);
+        const unsigned int w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { acc[2 * e] += __uint_as_float(w4[e] << 16); acc[2 * e + 1] += __uint_as_float(w4[e] & 0xffff0000u); }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[rl][gq][e] = acc[e];
+    __syncthreads();
+    if (rl == 0 && c < a.cols) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t += part[k][gq][e];
+        a.part[(long)by * a.cols + c + e] = t;
+      }
+    }
+  } else {
+    const int c = bx * 32 + gq;
+    float acc = 0.f;
+    if (c < a.cols) {
+      if (a.kind == 0) { const float* x = (const float*)a.x; for (long r = r0 + rl; r < r1; r += 8) acc += x[r * a.ld + c]; }
+      else { const unsigned short* x = (const unsigned short*)a.x; for (long r = r0 + rl; r < r1; r += 8) acc += bf2f(x[r * a.ld + c]); }
+    }
+    part[rl][gq][0] = acc;
+    __syncthreads();
+    if (rl == 0 && c < a.cols) {
+      float t = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t += part[k][gq][0];
+      a.part[(long)by * a.cols + c] = t;
+    }
+  }
+}
+
+// stage 2: thread = one column of one problem; the only writer of out[c] in this launch (the entry point checks that the outputs of a group are disjoint)
+__global__ __launch_bounds__(256) void colsum_ordered_final_kernel(OrdColsumGroup g) {
+  int pi = 0;
+  for (int i = 1; i < g.n; ++i) if ((int)blockIdx.x >= g.p[i].blk2_start) pi = i;
+  const OrdColsumProblem& a = g.p[pi];
+  const int c = (blockIdx.x - a.blk2_start) * 256 + threadIdx.x;
+  if (c >= a.cols) return;
+  float t = 0.f;
+  for (int k = 0; k < a.chunks; ++k) t += a.part[(long)k * a.cols + c];
+  a.out[c] += t;
+}
+
+// Ordered relnet_reduce_scalar: workgroup b of nb = min(64, ceil(n / 4096)) (a function of n) sums x[b 256 + t + i nb 256] per thread ascending i, the
+// wavefront by the xor butterfly 32, 16, .. 1, the workgroup ((w0 + w1) + w2) + w3, times the scale -> partial b; then out = ((0 + p0) + p1) + ...
+constexpr int kOrdScalarBlocks = 64;
+__global__ __launch_bounds__(256) void reduce_scalar_ordered_partial_kernel(const float* x, long n, float scale, int mode, float* part) {
+  __shared__ float sp[4];
+  float acc = 0.f;
+  const long stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) acc += mode ? (x[i] >= 0.f ? 1.f : 0.f) : x[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sp[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (mode ? 1.f : scale) * (((sp[0] + sp[1]) + sp[2]) + sp[3]);
+}
+__global__ __launch_bounds__(64) void reduce_scalar_ordered_final_kernel(const float* part, int nb, float* out) {
+  if (threadIdx.x != 0) return;
+  float t = 0.f;
+  for (int k = 0; k < nb; ++k) t += part[k];
+  out[0] = t;
+}
 
 // Adjoint of a stride-s 1x1 convolution's input sampling (x[:, ::s, ::s, :]): the low-resolution data gradient goes to the sampled pixels
 // of a full-resolution map, every other pixel is zero -- one pass that also applies the ReLU mask of the map's producer when that map has no
@@ -436,6 +541,69 @@ extern "C" int relnet_colsum_add_grouped(const void* const* xs, const long* lds,
   }
   colsum_add_grouped_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(g);
   return check_launch("relnet_colsum_add_grouped");
+}
+
+// ---- ordered (deterministic) entry points ---------------------------------------------------------------
+static long ord_colsum_chunks(long rows, long* rpb_out) {
+  long nchunk = (rows + 511) / 512;
+  nchunk = nchunk < 1 ? 1 : (nchunk > 128 ? 128 : nchunk);
+  const long rpb = (rows + nchunk - 1) / nchunk;
+  if (rpb_out) *rpb_out = rpb;
+  return (rows + rpb - 1) / rpb;
+}
+
+// bytes of workspace one [rows, cols] problem needs (a multiple of 16); a grouped launch needs the sum over its problems
+extern "C" long relnet_colsum_ordered_workspace_bytes(long rows, int cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  return ((ord_colsum_chunks(rows, nullptr) * cols * (long)sizeof(float) + 15) / 16) * 16;
+}
+
+extern "C" int relnet_colsum_add_grouped_ordered(const void* const* xs, const long* lds, const long* rows, const int* cols, const int* dtypes,
+                                                 float* const* outs, int n, void* workspace, long workspace_bytes, void* stream) {
+  RELNET_REQUIRE(xs && lds && rows && cols && dtypes && outs && workspace && n > 0 && n <= 16, "relnet_colsum_add_grouped_ordered: 1..16 problems and a workspace, got n = %d", n);
+  RELNET_REQUIRE((((uintptr_t)workspace) & 15) == 0, "relnet_colsum_add_grouped_ordered: the workspace must be 16-byte aligned");
+  OrdColsumGroup g;
+  g.n = n;
+  long used = 0;
+  int blocks = 0, blocks2 = 0;
+  for (int i = 0; i < n; ++i) {
+    RELNET_REQUIRE(xs[i] && outs[i] && rows[i] > 0 && cols[i] > 0 && lds[i] >= cols[i], "relnet_colsum_add_grouped_ordered: bad operand %d", i);
+    RELNET_REQUIRE(dtypes[i] == RELNET_F32 || dtypes[i] == RELNET_BF16, "relnet_colsum_add_grouped_ordered: unknown dtype %d of problem %d", dtypes[i], i);
+    // a plain read-modify-write per column: two problems of one launch must not share an output word (the caller splits such a group)
+    for (int j = 0; j < i; ++j)
+      RELNET_REQUIRE(outs[i] + cols[i] <= outs[j] || outs[j] + cols[j] <= outs[i],
+                     "relnet_colsum_add_grouped_ordered: the outputs of problems %d and %d overlap; issue them in separate launches", j, i);
+    OrdColsumProblem& p = g.p[i];
+    p.x = xs[i]; p.out = outs[i]; p.ld = lds[i]; p.rows = rows[i]; p.cols = cols[i];
+    p.chunks = (int)ord_colsum_chunks(rows[i], &p.rows_per_block);
+    p.kind = dtypes[i] == RELNET_F32 ? 0 : ((cols[i] % 8 == 0 && lds[i] % 8 == 0 && (((uintptr_t)xs[i]) & 15) == 0) ? 2 : 1);
+    p.col_blocks = p.kind == 2 ? (cols[i] / 8 + 31) / 32 : (cols[i] + 31) / 32;
+    p.part = (float*)((char*)workspace + used);
+    used += relnet_colsum_ordered_workspace_bytes(rows[i], cols[i]);
+    p.blk_start = blocks; p.blk2_start = blocks2;
+    blocks += p.col_blocks * p.chunks;
+    blocks2 += (cols[i] + 255) / 256;
+  }
+  RELNET_REQUIRE(used <= workspace_bytes, "relnet_colsum_add_grouped_ordered: the workspace holds %ld bytes, the group needs %ld", workspace_bytes, used);
+  colsum_ordered_partial_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(g);
+  colsum_ordered_final_kernel<<<(unsigned)blocks2, 256, 0, (hipStream_t)stream>>>(g);
+  return check_launch("relnet_colsum_add_grouped_ordered");
+}
+
+extern "C" int relnet_colsum_add_ordered(const void* x, long ld, long rows, int cols, int dtype, float* out, void* workspace, long workspace_bytes,
+                                         void* stream) {
+  return relnet_colsum_add_grouped_ordered(&x, &ld, &rows, &cols, &dtype, &out, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" long relnet_reduce_scalar_workspace_bytes(void) { return (long)kOrdScalarBlocks * sizeof(float); }
+
+extern "C" int relnet_reduce_scalar_ordered(const float* x, long n, float scale, int mode, float* out, void* workspace, void* stream) {
+  RELNET_REQUIRE(x && out && workspace && n > 0 && (mode == 0 || mode == 1), "relnet_reduce_scalar_ordered: bad arguments");
+  long blocks = (n + 4095) / 4096;
+  blocks = blocks < 1 ? 1 : (blocks > kOrdScalarBlocks ? kOrdScalarBlocks : blocks);
+  reduce_scalar_ordered_partial_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, n, scale, mode, (float*)workspace);
+  reduce_scalar_ordered_final_kernel<<<1, 64, 0, (hipStream_t)stream>>>((const float*)workspace, (int)blocks, out);
+  return check_launch("relnet_reduce_scalar_ordered");
 }
 
 extern "C" int relnet_sgd_update(float* w, float* mom, const float* grad, void* w_bf16, long n, float lr, float momentum,

@@ -331,8 +331,15 @@ static int wgrad_fill(const relnet_wgrad_desc& d, int bm, WgradProblem* out) {
 // copy, capture safe).
 extern "C" long relnet_wgrad_workspace_bytes(int n) { return (long)sizeof(WgradProblem) * (n > 0 ? n : 0); }
 
-extern "C" int relnet_wgrad_grouped(const relnet_wgrad_desc* descs, int n, void* table_workspace, void* stream) {
-  RELNET_REQUIRE(descs && n > 0 && table_workspace, "relnet_wgrad_grouped: bad arguments");
+static bool wgrad_writers_overlap(const relnet_wgrad_desc& a, const relnet_wgrad_desc& b) {
+  const float* a0 = a.dw; const float* a1 = a0 + (long)(a.Cout - 1) * a.dw_ld + (long)a.ks * a.ks * a.Cin;
+  const float* b0 = b.dw; const float* b1 = b0 + (long)(b.Cout - 1) * b.dw_ld + (long)b.ks * b.ks * b.Cin;
+  return a0 < b1 && b0 < a1;
+}
+
+// workgroups: size of the persistent grid of THIS launch (0: the relnet_wgrad_tune value, or one per CU).  tiles_mode: 0 = stream-K shares,
+// 2 = whole tiles when the writers are disjoint (else the atomics stay), 3 = whole tiles, the caller has made the writers disjoint.
+static int wgrad_grouped_launch(const relnet_wgrad_desc* descs, int n, void* table_workspace, int workgroups, int tiles_mode, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   // 128-row tiles only when no layer of the group has more rows (half of a 256-row tile would multiply zeros)
   int max_cout = 0;
@@ -357,7 +364,7 @@ extern "C" int relnet_wgrad_grouped(const relnet_wgrad_desc* descs, int n, void*
       c.offset += c.n; c.n = 0;
     }
   }
-  int blocks = g_wgrad_blocks > 0 ? g_wgrad_blocks : 256;
+  int blocks = workgroups > 0 ? workgroups : (g_wgrad_blocks > 0 ? g_wgrad_blocks : 256);
   if (units < blocks) blocks = (int)units;
   // whole-tile shares (no atomics, bit-identical reruns): OPT-IN (g_wgrad_tiles = 2).  Built in round 6 on the estimate that the atomic flush was 0.5 of the
   // 0.77 ms the seven launches of a one-image step take; measured, same box (tools/scripts/r06_ab3.sh): one image 7.16 ms with stream-K shares, 8.14 ms with
@@ -366,12 +373,10 @@ extern "C" int relnet_wgrad_grouped(const relnet_wgrad_desc* descs, int n, void*
   // into disjoint memory (checked here; otherwise the atomics stay).  g_wgrad_tiles: 0 / 1 = stream-K shares, 2 = whole tiles whenever the writers are disjoint
   bool disjoint = true;
   for (int i = 0; i < n && disjoint; ++i)
-    for (int j = i + 1; j < n && disjoint; ++j) {
-      const float* a0 = descs[i].dw; const float* a1 = a0 + (long)(descs[i].Cout - 1) * descs[i].dw_ld + (long)descs[i].ks * descs[i].ks * descs[i].Cin;
-      const float* b0 = descs[j].dw; const float* b1 = b0 + (long)(descs[j].Cout - 1) * descs[j].dw_ld + (long)descs[j].ks * descs[j].ks * descs[j].Cin;
-      if (a0 < b1 && b0 < a1) disjoint = false;
-    }
-  const bool whole = disjoint && g_wgrad_tiles == 2;
+    for (int j = i + 1; j < n && disjoint; ++j)
+      if (wgrad_writers_overlap(descs[i], descs[j])) disjoint = false;
+  RELNET_REQUIRE(tiles_mode != 3 || disjoint, "relnet_wgrad_grouped_ex: deterministic launch with overlapping writers");
+  const bool whole = disjoint && tiles_mode >= 2;
   (void)max_slabs;
   if (whole && tiles < blocks) blocks = (int)tiles;
   const int total_tiles = whole ? (int)tiles : 0;
@@ -392,4 +397,32 @@ extern "C" int relnet_wgrad_grouped(const relnet_wgrad_desc* descs, int n, void*
     else wgrad_streamk_kernel<2, false><<<blocks, 256, lds, s>>>(tb, n, (int)units, g_wgrad_mode, total_tiles);
   }
   return check_launch("relnet_wgrad_grouped");
+}
+
+extern "C" int relnet_wgrad_grouped(const relnet_wgrad_desc* descs, int n, void* table_workspace, void* stream) {
+  RELNET_REQUIRE(descs && n > 0 && table_workspace, "relnet_wgrad_grouped: bad arguments");
+  return wgrad_grouped_launch(descs, n, table_workspace, 0, g_wgrad_tiles == 2 ? 2 : 0, stream);
+}
+
+// relnet_wgrad_grouped with the launch's grid size as an ARGUMENT (workgroups, 0 = default; no process-wide knob to set and restore) and the
+// deterministic form: deterministic != 0 selects whole-tile shares -- one workgroup owns an output tile and walks its pixel slabs in ascending order,
+// a plain read-modify-write flush, the same bits whatever the grid -- and NEVER falls back to the atomics: layers that accumulate into overlapping
+// memory (the same weight used twice) are split into consecutive launches with disjoint writers, in queue order, so the order of their sums is
+// the order of the queue.  Launch k uses the table slots from its first layer's index on: the workspace size does not change.
+extern "C" int relnet_wgrad_grouped_ex(const relnet_wgrad_desc* descs, int n, void* table_workspace, int workgroups, int deterministic, void* stream) {
+  RELNET_REQUIRE(descs && n > 0 && table_workspace && workgroups >= 0, "relnet_wgrad_grouped_ex: bad arguments");
+  if (!deterministic) return wgrad_grouped_launch(descs, n, table_workspace, workgroups, g_wgrad_tiles == 2 ? 2 : 0, stream);
+  int first = 0;
+  while (first < n) {
+    int last = first + 1;                          // [first, last): the longest run whose writers are pairwise disjoint
+    for (; last < n; ++last) {
+      bool clash = false;
+      for (int j = first; j < last && !clash; ++j) clash = wgrad_writers_overlap(descs[j], descs[last]);
+      if (clash) break;
+    }
+    const int rc = wgrad_grouped_launch(descs + first, last - first, (char*)table_workspace + relnet_wgrad_workspace_bytes(first), workgroups, 3, stream);
+    if (rc != 0) return rc;
+    first = last;
+  }
+  return 0;
 }

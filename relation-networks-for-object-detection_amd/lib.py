@@ -170,6 +170,17 @@ _SIGNATURES = {
     'relnet_grad_stats': (C.c_int, [_vp, _vp, _i, _vp, _l, _l, _vp]),
     'relnet_grad_guard_decide': (C.c_int, [_vp, _l, _d, _vp, _vp]),
     'relnet_sgd_update_guarded': (C.c_int, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _vp, _f, _vp]),
+    # deterministic training mode: ordered forms of the atomic accumulations (include/relnet_hip.h, last section)
+    'relnet_roi_pool_bwd_ordered': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l] + [_i] * 7 + [_f, _i, _i, _vp]),
+    'relnet_colsum_ordered_workspace_bytes': (C.c_long, [_l, _i]),
+    'relnet_colsum_add_ordered': (C.c_int, [_vp, _l, _l, _i, _i, _vp, _vp, _l, _vp]),
+    'relnet_colsum_add_grouped_ordered': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _l, _vp]),
+    'relnet_reduce_scalar_workspace_bytes': (C.c_long, []),
+    'relnet_reduce_scalar_ordered': (C.c_int, [_vp, _l, _f, _i, _vp, _vp, _vp]),
+    'relnet_geometry_bias_bwd_workspace_bytes': (C.c_long, [_i, _i]),
+    'relnet_geometry_bias_bwd_ordered': (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp]),
+    'relnet_lnms_take_bwd_ordered': (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'relnet_wgrad_grouped_ex': (C.c_int, [_vp, _i, _vp, _i, _i, _vp]),
 }
 
 

@@ -347,14 +347,25 @@ def roi_pool(data, rois, pooled=(7, 7), spatial_scale=0.0625, channels_last_out=
     return (out, arg) if want_argmax else out
 
 
-def roi_pool_bwd(grad_out, argmax, rois, in_shape, batch_index_base=0, channels_last=False):
+def roi_pool_bwd(grad_out, argmax, rois, in_shape, batch_index_base=0, channels_last=False, deterministic=False, spatial_scale=0.0625):
     """Adjoint of roi_pool: grad_out / argmax logical [R,C,PH,PW] with IDENTICAL strides (as returned by
     roi_pool(want_argmax=True)); in_shape (B,C,H,W) -> fp32 gradient of the feature map, logical [B,C,H,W]; memory NCHW, or
-    NHWC with channels_last (coalesced atomics; `.permute(0, 2, 3, 1)` of the result is then contiguous)."""
+    NHWC with channels_last (coalesced atomics; `.permute(0, 2, 3, 1)` of the result is then contiguous).
+    deterministic: the ordered gather form (relnet_roi_pool_bwd_ordered) -- every word is the fp32 sum of its contributions in ascending
+    (roi, ph, pw) order, no atomics, the same bits on every call; it needs the forward's spatial_scale to find a cell's candidate bins."""
     _chk(grad_out, argmax, rois)
     assert argmax.dtype == torch.int32 and tuple(grad_out.stride()) == tuple(argmax.stride()) and grad_out.shape == argmax.shape
     B, Cc, H, W = in_shape
     R, _, PH, PW = grad_out.shape
+    if deterministic:
+        assert rois.dtype == torch.float32 and rois.is_contiguous()
+        if channels_last:
+            gin = torch.empty((B, H, W, Cc), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2)        # every word is written
+        else:
+            gin = torch.empty((B, Cc, H, W), device=grad_out.device, dtype=torch.float32)
+        _lib.call('relnet_roi_pool_bwd_ordered', grad_out.data_ptr(), argmax.data_ptr(), _strides4(grad_out), rois.data_ptr(), gin.data_ptr(),
+                  gin.stride(0), gin.stride(1), gin.stride(3), B, H, W, R, Cc, PH, PW, float(spatial_scale), batch_index_base, _dt(grad_out), _stream())
+        return gin
     if channels_last:
         gin = torch.zeros((B, H, W, Cc), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2)
         # (relnet_roi_pool_bwd_cl: from 8 images x 256 channels up, one workgroup per (image, 8 channels) accumulates its slab in LDS -- no global atomics)
@@ -1447,6 +1458,19 @@ def lnms_scatter_bwd(d_sorted, rank_idx, N):
     return d_prob
 
 
+def lnms_take_bwd_ordered(d_x, rank_idx, N):
+    """Ordered adjoint of the learn-NMS branch's take: d_x [B,C,F,128] bf16 / fp32, rank_idx [B,C,F] int32 (distinct within one (image, class),
+    negative = padding) -> d_emb [B*N,128] fp32, every row the fp32 sum of the rows of d_x that name the roi in ascending flat source index
+    (relnet_lnms_take_bwd_ordered; no atomics, unlike index_add_)."""
+    _chk(d_x, rank_idx)
+    B, Cn, F, D = d_x.shape
+    assert D == 128 and d_x.is_contiguous() and d_x.dtype in (torch.bfloat16, torch.float32)
+    assert rank_idx.shape == (B, Cn, F) and rank_idx.dtype == torch.int32 and rank_idx.is_contiguous()
+    d_emb = torch.empty((B * N, 128), device=d_x.device, dtype=torch.float32)
+    _lib.call('relnet_lnms_take_bwd_ordered', d_x.data_ptr(), rank_idx.data_ptr(), d_emb.data_ptr(), B, N, Cn, F, _dt(d_x), _stream())
+    return d_emb
+
+
 class WgradQueue(object):
     """Weight-gradient products collected for ONE grouped launch (csrc/wgrad.hip: stream-K over the (layer, tile, slab) units
     of all queued layers).  `add` has the signature of `wgrad_tn`; `flush` launches what is queued.  The queue keeps the
@@ -1454,8 +1478,11 @@ class WgradQueue(object):
     place before the flush: `flush` checks their version counters before anything is launched (not `out`'s: a view of the flat
     gradient buffer shares its counter with the other slices, which are written while products are queued)."""
 
-    def __init__(self):
+    def __init__(self, deterministic=False):
+        """deterministic: every flush runs whole-tile shares (relnet_wgrad_grouped_ex: no float atomics, the same bits on every run; layers
+        that accumulate into overlapping memory are split into consecutive launches in queue order)."""
         self.items, self.keep, self.versions = [], [], []
+        self.deterministic = bool(deterministic)
 
     def add(self, dy2d, x, out, row_scale=None, cout=None, conv=None):
         _chk(dy2d, x, out, row_scale)
@@ -1503,29 +1530,28 @@ class WgradQueue(object):
         lib = _lib.load()
         ws = torch.empty(int(lib.relnet_wgrad_workspace_bytes(n)), device=keep[0][0].device, dtype=torch.uint8)
         import ctypes
-        if workgroups:
-            lib.relnet_wgrad_tune(int(workgroups), 0, 0)
-        try:
+        if workgroups or self.deterministic:
+            # the grid size travels as an ARGUMENT of this launch: no process-wide relnet_wgrad_tune value is set here, so whatever a tool
+            # had set (workgroups, ablation bits, wave rows) is still in force afterwards instead of being zeroed
+            _lib.call('relnet_wgrad_grouped_ex', ctypes.addressof(arr), n, ws.data_ptr(), int(workgroups), int(self.deterministic), _stream(), tag='n%d' % n)
+        else:
             _lib.call('relnet_wgrad_grouped', ctypes.addressof(arr), n, ws.data_ptr(), _stream(), tag='n%d' % n)
-        finally:
-            if workgroups:
-                lib.relnet_wgrad_tune(0, 0, 0)
         return ws          # the caller may hold on to it; stream order already protects it from reuse on this stream
 
 
-def wgrad_tn(dy2d, x, out=None, row_scale=None, cout=None, conv=None):
+def wgrad_tn(dy2d, x, out=None, row_scale=None, cout=None, conv=None, deterministic=False):
     """Weight gradient  out [Cout, K] fp32 += row_scale^2 * dy2d^T X  straight from the pixel-major operands (csrc/wgrad.hip:
     LDS-transposed MFMA fragments, implicit im2col, stream-K over (tile, 64-pixel slab) units; no transposed copies).
     dy2d [P, >= Cout] bf16 (row stride a multiple of 8; columns >= cout must be zero padding).
     conv None: x [P, K] bf16 rows;  conv = (ksize, stride, dil, pad): x [B, Hin, Win, Cin] NHWC (any pixel stride) and
     dy2d the [B * Hout * Wout, Cout] gradient of that convolution's output, K = ksize^2 Cin in pack_conv_weight order.
     out None: a fresh zero tensor is returned (otherwise accumulated into `out`, e.g. a view of the flat gradient buffer).
-    One layer per launch; `WgradQueue` groups many layers into one."""
+    One layer per launch; `WgradQueue` groups many layers into one.  deterministic: see WgradQueue."""
     if out is None:
         cin = x.shape[-1]
         k = 1 if conv is None else conv[0]
         out = torch.zeros((dy2d.shape[1] if cout is None else cout, k * k * cin), device=dy2d.device, dtype=torch.float32)
-    q = WgradQueue()
+    q = WgradQueue(deterministic=deterministic)
     q.add(dy2d, x, out, row_scale, cout, conv)
     q.flush()
     return out
@@ -1577,9 +1603,11 @@ def relation_attention_bwd(q, k, kt, vw, bias, dy, y, bout, qt, dyt, M, heads=16
     return dq, dk, dvw, prob, dlog
 
 
-def geometry_bias_bwd(boxes, bias, dlog, M, divisors=None, fast=False, out=None):
+def geometry_bias_bwd(boxes, bias, dlog, M, divisors=None, fast=False, out=None, deterministic=False):
     """boxes [B,N,4|5]; bias / dlog [B,16,N,Mpad] fp32 -> (d pair_pos_fc1 weight [16,64], d bias [16]) fp32.
-    out = (dwp, dbp): contiguous fp32 tensors the kernel ACCUMULATES into (atomic adds; e.g. views of a flat gradient buffer)."""
+    out = (dwp, dbp): contiguous fp32 tensors the kernel ACCUMULATES into (atomic adds; e.g. views of a flat gradient buffer).
+    deterministic: relnet_geometry_bias_bwd_ordered -- per-wavefront / per-workgroup partial sums into a workspace, then one fixed-order
+    sum into dwp / dbp: the same bits on every call (no atomics)."""
     _chk(boxes, bias, dlog)
     assert boxes.dtype == torch.float32 and boxes.is_contiguous()
     B, N, bs = boxes.shape
@@ -1592,6 +1620,12 @@ def geometry_bias_bwd(boxes, bias, dlog, M, divisors=None, fast=False, out=None)
     else:
         dwp = torch.zeros((16, 64), device=boxes.device, dtype=torch.float32)
         dbp = torch.zeros((16,), device=boxes.device, dtype=torch.float32)
+    if deterministic:
+        nbytes = int(_lib.load().relnet_geometry_bias_bwd_workspace_bytes(B, N))
+        ws = torch.empty(nbytes // 4, device=boxes.device, dtype=torch.float32)          # (needs no initialisation: every slot that is read was written first)
+        _lib.call('relnet_geometry_bias_bwd_ordered', boxes.data_ptr(), bs, 1 if bs == 5 else 0, bias.data_ptr(), dlog.data_ptr(),
+                  div.data_ptr(), dwp.data_ptr(), dbp.data_ptr(), B, N, M, bias.shape[-1], int(fast), ws.data_ptr(), nbytes, _stream())
+        return dwp, dbp
     _lib.call('relnet_geometry_bias_bwd', boxes.data_ptr(), bs, 1 if bs == 5 else 0, bias.data_ptr(), dlog.data_ptr(),
               div.data_ptr(), dwp.data_ptr(), dbp.data_ptr(), B, N, M, bias.shape[-1], int(fast), _stream())
     return dwp, dbp

@@ -183,11 +183,13 @@ class GradSink(object):
                bias gradients, accumulated by relnet_colsum_add (train_ops.colsum_add)
       dwp, dbp fp32 views [16, 64] / [16] of pair_pos_fc1's gradient: the geometry backward accumulates into them atomically
       scratch  callable(name, shape, dtype) -> persistent ZERO-initialised buffer (pad columns of the transposed operands stay zero
-               from step to step: no per-step fill)"""
+               from step to step: no per-step fill)
+      deterministic  the geometry backward accumulates dwp / dbp in a fixed order instead (no atomics)"""
 
-    def __init__(self, wcat_t, resid, wgrad, b_qk, b_out, dwp, dbp, scratch):
+    def __init__(self, wcat_t, resid, wgrad, b_qk, b_out, dwp, dbp, scratch, deterministic=False):
         self.wcat_t, self.resid, self.wgrad, self.b_qk, self.b_out, self.dwp, self.dbp, self.scratch = \
             wcat_t, resid, wgrad, b_qk, b_out, dwp, dbp, scratch
+        self.deterministic = bool(deterministic)      # the geometry backward's ordered form (ops.geometry_bias_bwd(deterministic=True)); the queues carry their own flag
 
 
 def attention_module_backward(roi_feat, rois, params, d_out, nongt_dim=None, index=1, dtype=None, packed=None, key_count=None,
@@ -268,7 +270,7 @@ def attention_module_backward(roi_feat, rois, params, d_out, nongt_dim=None, ind
     if sink is not None and dtype == torch.bfloat16:
         # ---- gradients straight into the trainer's buffers (GradSink): one pack kernel, ONE projection-backward GEMM with the residual
         # gradient in its epilogue, ONE queued weight-gradient product for [Wq; Wk; Wout], two column-sum kernels for the biases
-        ops.geometry_bias_bwd(bx, bias, dlog, M, fast=True, out=(sink.dwp, sink.dbp))
+        ops.geometry_bias_bwd(bx, bias, dlog, M, fast=True, out=(sink.dwp, sink.dbp), deterministic=sink.deterministic)
         a3 = packed if packed is not None else ops.relation_bwd_pack(dq, dk, dvw)   # [B, N, 3 d] bf16 = (dQ | dK | dVW), key blocks zero past M
         a3_2d = a3.view(B * N, 3 * d)
         d_f = ops.gemm_nt(a3_2d, sink.wcat_t, resid=None if sink.resid is None else sink.resid.reshape(B * N, Fd)).reshape(B, N, Fd)

@@ -46,6 +46,10 @@ class TrainConfig(Config):
     relation = True               # two relation modules in the 2FC head (False: the plain head of resnet_v1_101_rcnn_learn_nms_1024_...)
     enable_ohem = True            # TRAIN.ENABLE_OHEM (False: SoftmaxOutput over all rois, bbox loss scaled by 1 / 300)
     fixed_params = None           # network.FIXED_PARAMS of the experiment file (None: dist.FIXED_PARAMS, the end2end yamls' list)
+    deterministic = False         # True: every float accumulation of the step whose order the hardware would decide (float atomics: ROI pooling
+                                  # backward, bias-gradient column sums, loss scalars, the geometry backward, the learn-NMS take adjoint, the
+                                  # stream-K weight-gradient flush) runs its ordered form -- two steps from the same state give the same bits
+                                  # (DESIGN.md section 9).  C4 graphs with ROIPooling only: dcn, roi_align and FPNTrainer are refused
 
 
 # workgroups of the RPN head's grouped weight-gradient launch on the side stream: a quarter of the chip, the head's kernels beside it keep
@@ -71,6 +75,19 @@ def all_reduce_sum(*buffers):
             dist.all_reduce(b, op=dist.ReduceOp.SUM)
         if buffers and buffers[0].is_cuda and dist.get_backend() != 'nccl':
             torch.cuda.synchronize()            # gloo on device tensors (one-GPU test path), see dist.BucketedAllReduce.finish
+
+
+def check_deterministic(cfg):
+    """cfg.deterministic covers the C4 graphs with ROIPooling.  The other pooling operators and the deformable convolutions still accumulate
+    with float atomics, whose order the hardware decides: refused by name rather than silently not reproducible."""
+    if not getattr(cfg, 'deterministic', False):
+        return
+    if getattr(cfg, 'fpn', False):
+        raise ValueError("deterministic training does not cover the FPN graphs: roi_pool_fpn_bwd (and roi_align_bwd with cfg.roi_align) accumulate with float atomics")
+    if getattr(cfg, 'dcn', False):
+        raise ValueError("deterministic training does not cover cfg.dcn: deformable_psroi_pool_bwd and deformable_col2im accumulate with float atomics")
+    if getattr(cfg, 'roi_align', False):
+        raise ValueError("deterministic training does not cover cfg.roi_align: roi_align_bwd accumulates with float atomics")
 
 
 class _Flat(object):
@@ -165,8 +182,10 @@ class Trainer(object):
         nms_pos_loss_map, nms_neg_loss_map): the output list of the reference's train graph, which metric.py's host classes take."""
         self.cfg = cfg or TrainConfig()
         check_pooling(self.cfg)
+        check_deterministic(self.cfg)
         self.device, self.im_hw = device, im_hw
         c = self.cfg
+        self.deterministic = bool(getattr(c, 'deterministic', False))       # read ONCE: every site below routes on this attribute
         dev = device
         f32 = lambda t: torch.as_tensor(t).to(dev, torch.float32).contiguous()
         self.fpn = bool(getattr(c, 'fpn', False))
@@ -283,8 +302,8 @@ class Trainer(object):
         # bucket completes (`_flush_wgrads`)
         self._anchor_step = torch.zeros(1, device=dev, dtype=torch.int64)
         self._side = torch.cuda.Stream(device=dev)
-        self._wq = ops.WgradQueue()
-        self._cq = T.ColsumQueue()
+        self._wq = ops.WgradQueue(deterministic=self.deterministic)
+        self._cq = T.ColsumQueue(deterministic=self.deterministic)
         # every data-parallel rank samples its own fg / bg anchor subsets (cfg.rank_in_anchor_seed = False: the same subsets on every
         # rank, what the two-rank gradient-sum check needs)
         self._rank, self._world = (0, 1) if not getattr(c, 'rank_in_anchor_seed', True) else ((torch.distributed.get_rank(), torch.distributed.get_world_size())
@@ -516,7 +535,7 @@ class Trainer(object):
             tgt = tgt_in.permute(0, 2, 3, 1).contiguous()
             wgt = wgt_in.permute(0, 2, 3, 1).contiguous()
             rpn_l1, d_delta = losses.smooth_l1_loss(delta, tgt, wgt, 3.0, 1.0 / c.rpn_batch_size)
-            out['rpn_bbox_loss'] = T.scalar_sum(rpn_l1, 1.0 / B)
+            out['rpn_bbox_loss'] = T.scalar_sum(rpn_l1, 1.0 / B, deterministic=self.deterministic)
             d_rpn = torch.cat([d_score.permute(0, 2, 3, 1), d_delta], 3).to(torch.bfloat16).contiguous()
             # -- proposals and their targets (no gradient: proposal.py:170-173, proposal_target.py:95-97)
             rois, _ = propose_batch(nchw(rpn[..., :na2]), nchw(rpn[..., na2:]), im_info, self.anchors, c.feat_stride,
@@ -540,7 +559,7 @@ class Trainer(object):
         def rpn_backward(conv4, r, d_rpn):
             # RPN head backward (joins the trunk at conv4), on the side stream beside ROI pooling / the 2FC head / the learn-NMS branch (launches of
             # <= 150 workgroups), and with it the two RPN weight gradients as their own grouped launch on RPN_WGRAD_WORKGROUPS workgroups
-            rq = ops.WgradQueue()
+            rq = ops.WgradQueue(deterministic=self.deterministic)
             wg = lambda n: self._wg(n)[:2] + (rq,)
             g_r, dw = T.conv1x1_bwd(r, self.w('rpn_out'), d_rpn, w_t=self.wt('rpn_out'), keep_splits=True, wgrad_to=wg('rpn_out'), relu_mask=r)
             T.colsum_add(d_rpn, *self._bg('rpn_out'))
@@ -616,7 +635,8 @@ class Trainer(object):
             d_feat = d_feat.permute(0, 2, 3, 1).to(bt)          # NHWC memory already: one conversion pass
         else:
             d_feat = ops.roi_pool_bwd(d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), argmax, r5,
-                                      (B, feat.shape[3], feat.shape[1], feat.shape[2]), channels_last=True)
+                                      (B, feat.shape[3], feat.shape[1], feat.shape[2]), channels_last=True,
+                                      deterministic=self.deterministic, spatial_scale=1.0 / c.feat_stride)
             d_feat = d_feat.permute(0, 2, 3, 1).to(bt)          # NHWC memory already: one conversion pass
         g = T.relu_bwd(d_feat, feat)
         d_x, dw = T.conv1x1_bwd(conv5, self.w('conv_new_1'), g, w_t=self.wt('conv_new_1'), keep_splits=True, wgrad_to=self._wg('conv_new_1'))
@@ -755,8 +775,8 @@ class Trainer(object):
         cls_prob, d_cls = losses.softmax_output(cls_score.view(B * R, -1), labels_ohem.reshape(-1), use_ignore=True, ignore_label=-1.0, group=R)
         d_cls = d_cls.view(B, R, -1)
         l1, d_bbox = losses.smooth_l1_loss(bbox_pred, bbox_target, weights_ohem, 1.0, 1.0 / box_norm)
-        out['bbox_loss'] = T.scalar_sum(l1, 1.0 / B)
-        out['num_ohem'] = T.scalar_sum(labels_ohem, count_nonneg=True)
+        out['bbox_loss'] = T.scalar_sum(l1, 1.0 / B, deterministic=self.deterministic)
+        out['num_ohem'] = T.scalar_sum(labels_ohem, count_nonneg=True, deterministic=self.deterministic)
         if self.metrics is not None:        # RCNNAcc / RCNNLogLoss / RCNNL1Loss (padding rows of a short proposal list have label -1: not counted)
             self.metrics.add_rcnn(cls_prob, labels_ohem.reshape(-1), l1)
             out['cls_prob'], out['bbox_loss_map'] = cls_prob.view(B, R, -1), l1
@@ -874,7 +894,8 @@ class Trainer(object):
             multi = sorted_score.unsqueeze(3) * cond
         target = ops.nms_multi_target(sorted_bbox, gt_boxes, sorted_score, num_gt, c.nms_target_thresh)
         pos, neg, d_multi = losses.nms_loss(multi, target, F, Tn, c.nms_loss_scale, c.nms_pos_scale, c.nms_eps)
-        lo = dict(nms_pos_loss=T.scalar_sum(pos, 1.0 / B), nms_neg_loss=T.scalar_sum(neg, 1.0 / B), nms_multi_score=multi, nms_multi_target=target,
+        det = self.deterministic
+        lo = dict(nms_pos_loss=T.scalar_sum(pos, 1.0 / B, deterministic=det), nms_neg_loss=T.scalar_sum(neg, 1.0 / B, deterministic=det), nms_multi_score=multi, nms_multi_target=target,
                   sorted_score=sorted_score, nms_rank_idx=rank_idx, nms_class_boxes=class_boxes)
         if self.metrics is not None:        # NMSLoss_pos / _neg (B images: one image = one executor in the reference), NMSAcc_pos / _neg
             self.metrics.add_nms(target, cond, pos, neg, B)
@@ -912,17 +933,20 @@ class Trainer(object):
         glo.zero_()
 
         def wg(dy2d, x2d):
-            ops.wgrad_tn(dy2d[:, :2048], x2d, out=gq.view(2048, 128))
-            ops.wgrad_tn(dy2d[:, 2048:], x2d, out=glo)
+            ops.wgrad_tn(dy2d[:, :2048], x2d, out=gq.view(2048, 128), deterministic=det)
+            ops.wgrad_tn(dy2d[:, 2048:], x2d, out=glo, deterministic=det)
         sink = GradSink(wcat_t, g.view(BC, F, 128), wg, self._bg('nms_qk_1'), None,
-                        self.W.view(self.W.grad, 'nms_pair_pos_fc1_1'), self.Bv.view(self.Bv.grad, 'nms_pair_pos_fc1_1'), self._scratch)
+                        self.W.view(self.W.grad, 'nms_pair_pos_fc1_1'), self.Bv.view(self.Bv.grad, 'nms_pair_pos_fc1_1'), self._scratch, deterministic=det)
         r = attention_module_backward(xr, cb, None, dY, nongt_dim=F, index=1, dtype=bt, packed=mod, cache=lcache, sink=sink)
         self.W.view(self.W.grad, 'nms_linear_out_1').view(16, 8, 128).add_(glo.view(16, 64, 128)[:, :8])
         T.colsum_add(g.view(BC * F, 128), *self._bg('nms_linear_out_1'))    # (dY's real columns are g's columns)
         d_x = r['d_roi_feat'].view(B, C, F, 128)                            # bf16: residual + module
         if fused and d_x.is_contiguous():
             d_rank = torch.zeros((F, 128), device=dev, dtype=torch.float32)                     # sum over (image, class): one column-sum launch (fp32 accumulation)
-            _lib.call('relnet_colsum_add', d_x.data_ptr(), F * 128, BC, F * 128, ops._dt(d_x), d_rank.data_ptr(), s_)
+            if det:
+                T.colsum_add(d_x.view(BC, F * 128), d_rank.view(-1), deterministic=True)
+            else:
+                _lib.call('relnet_colsum_add', d_x.data_ptr(), F * 128, BC, F * 128, ops._dt(d_x), d_rank.data_ptr(), s_)
             T._wg_call(self._wg('nms_rank'), d_rank.to(bt), self.rank_emb)
             T.colsum_add(d_rank, *self._bg('nms_rank'))
         else:
@@ -931,7 +955,12 @@ class Trainer(object):
         if fused and d_x.dtype == bt and d_x.is_contiguous() and C <= 128:
             d_emb = torch.empty((B * N, 128), device=dev, dtype=bt)          # every row written: gathered per roi over the classes that rank it (fp32 sums)
             _lib.call('relnet_lnms_take_bwd', d_x.data_ptr(), rank_idx.data_ptr(), d_emb.data_ptr(), B, N, C, F, s_)
+        elif det and d_x.is_contiguous() and d_x.dtype in (bt, torch.float32):
+            # the ordered gather for the operands the kernel above does not take (no index_add_: torch's scatter adds with float atomics)
+            d_emb = ops.lnms_take_bwd_ordered(d_x, rank_idx, N).to(bt)
         else:
+            if det:
+                raise ValueError("deterministic training: the learn-NMS take adjoint needs a contiguous bf16 / fp32 gradient (index_add_ uses float atomics)")
             d_emb = torch.zeros((B * N, 128), device=dev, dtype=torch.float32)
             flat = (rank_idx.long() + (torch.arange(B, device=dev) * N).view(B, 1, 1)).view(-1)
             d_emb.index_add_(0, flat, d_x.reshape(-1, 128).float())                             # take() backward (a roi is ranked in up to 80 classes: fp32 sums)
@@ -981,7 +1010,8 @@ class Trainer(object):
         g3 = self.W.grad[oq:oq + (sq[0] + so[0]) * sq[1]].view(sq[0] + so[0], sq[1])      # d[Wq; Wk; Wout], adjacent slices of the flat buffer
         sink = GradSink(wcat_t, g, lambda dy2d, x2d: T._wg_call((g3, None, self._wq), dy2d, x2d),
                         self._bg('qk_%d' % i), self._bg('linear_out_%d' % i),
-                        self.W.view(self.W.grad, 'pair_pos_fc1_%d' % i), self.Bv.view(self.Bv.grad, 'pair_pos_fc1_%d' % i), self._scratch)
+                        self.W.view(self.W.grad, 'pair_pos_fc1_%d' % i), self.Bv.view(self.Bv.grad, 'pair_pos_fc1_%d' % i), self._scratch,
+                        deterministic=self.deterministic)
         r = attention_module_backward(f, rois, None, g, nongt_dim=N, index=i, dtype=torch.bfloat16, packed=mod, key_count=key_count,
                                       cache=cache, sink=sink)
         return r['d_roi_feat']
@@ -1340,6 +1370,7 @@ class FPNTrainer(Trainer):
     def __init__(self, params, cfg=None, device='cuda', metrics=None, guard=None):
         cfg = cfg or TrainConfig()
         cfg.fpn = True
+        check_deterministic(cfg)        # (before anything is built: the FPN pooling backward has no ordered form)
         Trainer.__init__(self, params, cfg, device, im_hw=None, metrics=metrics, guard=guard)
 
     def _forward_backward_impl(self, data, im_info, gt_boxes, proposals, num_gt=None, num_proposals=None):

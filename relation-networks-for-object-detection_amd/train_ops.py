@@ -41,20 +41,53 @@ def strided_scatter(low, shape, stride, mask=None):
     return out
 
 
+def colsum_ordered_workspace(problems, device):
+    """Workspace of one ordered column-sum launch over `problems` = [(rows, cols), ...] (float32 words; needs no initialisation: every partial
+    sum that is read was written first).  Sized by the library, like grad_guard_workspace."""
+    lib = _lib.load()
+    nbytes = sum(int(lib.relnet_colsum_ordered_workspace_bytes(int(r), int(c))) for r, c in problems)
+    return torch.empty(max(nbytes, 16) // 4, device=device, dtype=torch.float32)
+
+
+def _colsum_ordered(items):
+    """items: [(x2 [rows, cols] bf16 / fp32 with a dense last dim, out fp32 [cols])], any number: ordered grouped launches of <= 16 problems whose
+    outputs do not overlap (a plain read-modify-write per column: two sums into the same bias go into consecutive launches, in queue order)."""
+    import ctypes as C
+    groups = []
+    for x, o in items:
+        lo, hi = o.data_ptr(), o.data_ptr() + 4 * o.numel()
+        if not groups or len(groups[-1]) == 16 or any(lo < h and l < hi for _, _, l, h in groups[-1]):
+            groups.append([])
+        groups[-1].append((x, o, lo, hi))
+    for grp in groups:
+        n = len(grp)
+        ws = colsum_ordered_workspace([(x.shape[0], x.shape[1]) for x, _, _, _ in grp], grp[0][0].device)
+        xs = (C.c_void_p * n)(*[x.data_ptr() for x, _, _, _ in grp])
+        lds = (C.c_long * n)(*[x.stride(0) for x, _, _, _ in grp])
+        rows = (C.c_long * n)(*[x.shape[0] for x, _, _, _ in grp])
+        cols = (C.c_int * n)(*[x.shape[1] for x, _, _, _ in grp])
+        dts = (C.c_int * n)(*[_dt(x) for x, _, _, _ in grp])
+        outs = (C.c_void_p * n)(*[o.data_ptr() for _, o, _, _ in grp])
+        _lib.call('relnet_colsum_add_grouped_ordered', xs, lds, rows, cols, dts, outs, n, ws.data_ptr(), ws.numel() * 4, _stream())
+
+
 class ColsumQueue(object):
     """Bias-gradient column sums collected for ONE grouped launch per gradient bucket (relnet_colsum_add_grouped, <= 16 problems per
     launch).  `add` keeps the operand alive until `flush`; operands the grouped kernel does not take (fp32, ragged widths) are summed at once.
-    The operand must not be modified in place before the flush: `flush` checks its version counter before anything is launched."""
+    The operand must not be modified in place before the flush: `flush` checks its version counter before anything is launched.
+    deterministic: the ordered kernels (relnet_colsum_add_grouped_ordered: no float atomics, a summation tree that depends on the operand's
+    shape only); they take every operand, so nothing is summed at once."""
 
-    def __init__(self):
+    def __init__(self, deterministic=False):
         self.items = []
+        self.deterministic = bool(deterministic)
 
     def __len__(self):
         return len(self.items)
 
     def add(self, x2, out):
         ok = (x2.dtype == torch.bfloat16 and x2.shape[1] % 8 == 0 and x2.stride(0) % 8 == 0 and x2.data_ptr() % 16 == 0)
-        if not ok:
+        if not ok and not self.deterministic:
             _lib.call('relnet_colsum_add', x2.data_ptr(), x2.stride(0), x2.shape[0], x2.shape[1], _dt(x2), out.data_ptr(), _stream())
             return
         self.items.append((x2, out, x2._version))
@@ -64,6 +97,9 @@ class ColsumQueue(object):
         items, self.items = self.items, []
         for x, _, v in items:
             assert x._version == v, "a queued bias-gradient operand %s was modified in place before the flush" % (tuple(x.shape),)
+        if self.deterministic:
+            _colsum_ordered([(x, o) for x, o, _ in items])
+            return items
         for i in range(0, len(items), 16):
             grp = items[i:i + 16]
             n = len(grp)
@@ -76,15 +112,19 @@ class ColsumQueue(object):
         return items            # (still referenced by the caller until the launch has been issued)
 
 
-def colsum_add(x, out, queue=None):
+def colsum_add(x, out, queue=None, deterministic=False):
     """out[c] += sum over all leading dims of x[..., c]  (bias gradient accumulated in place; x bf16 / fp32 with a dense last dim,
-    out fp32 [C] -- a view of the flat gradient buffer).  queue (ColsumQueue): the sum is deferred to the queue's grouped launch."""
+    out fp32 [C] -- a view of the flat gradient buffer).  queue (ColsumQueue): the sum is deferred to the queue's grouped launch (and is
+    ordered when the queue is).  deterministic (no queue): the ordered kernel, at once -- the same tree as inside a group."""
     C = x.shape[-1]
     assert out.dtype == torch.float32 and out.numel() == C and out.is_contiguous() and x.stride(-1) == 1
     x2 = x.reshape(-1, C)
     _chk(x2, out)
     if queue is not None:
         queue.add(x2, out)
+        return
+    if deterministic:
+        _colsum_ordered([(x2, out)])
         return
     _lib.call('relnet_colsum_add', x2.data_ptr(), x2.stride(0), x2.shape[0], C, _dt(x2), out.data_ptr(), _stream())
 
@@ -193,13 +233,18 @@ def wgrad(dy2d, x2d, keep_splits=False):
     return part.sum(0) if s > 1 else part[0]
 
 
-def scalar_sum(x, scale=1.0, count_nonneg=False):
+def scalar_sum(x, scale=1.0, count_nonneg=False, deterministic=False):
     """0-dim fp32 tensor = scale * x.sum() (or the number of entries >= 0): relnet_reduce_scalar, one launch (the loss values /
-    OHEM count a step reports; torch needs sum + div / ge + sum)."""
+    OHEM count a step reports; torch needs sum + div / ge + sum).  deterministic: relnet_reduce_scalar_ordered (workgroup sums into a
+    workspace, then their ascending sum: no float atomic)."""
     _chk(x)
     if x.dtype != torch.float32 or not x.is_contiguous():
         return (x >= 0).sum().float() if count_nonneg else x.sum() * scale
     out = torch.empty((), device=x.device, dtype=torch.float32)
+    if deterministic:
+        ws = torch.empty(int(_lib.load().relnet_reduce_scalar_workspace_bytes()) // 4, device=x.device, dtype=torch.float32)
+        _lib.call('relnet_reduce_scalar_ordered', x.data_ptr(), x.numel(), float(scale), int(bool(count_nonneg)), out.data_ptr(), ws.data_ptr(), _stream())
+        return out
     _lib.call('relnet_reduce_scalar', x.data_ptr(), x.numel(), float(scale), int(bool(count_nonneg)), out.data_ptr(), _stream())
     return out
 
