@@ -1631,6 +1631,27 @@ def geometry_bias_bwd(boxes, bias, dlog, M, divisors=None, fast=False, out=None,
     return dwp, dbp
 
 
+def deformable_col2im(dcol, data, offset, kernel=(3, 3), stride=(1, 1), dilate=(1, 1), pad=(0, 0), num_deformable_group=1,
+                      grad_data=None, grad_offset=None):
+    """The sampling half of deformable_conv_bwd (nn/deformable_im2col.cuh:313-351, 420-470): dcol [B*Ho*Wo, >= kh*kw*C] (fp32 or bf16, column
+    tap*C + c, unit column stride), data logical [B,C,H,W], offset fp32 logical [B,2*kh*kw*dg,Ho,Wo] -> (grad_data, grad_offset), both fp32 and
+    ACCUMULATED INTO: given tensors (logical [B,C,H,W] / offset's shape, any strides) are added to, missing ones are zero-filled NHWC."""
+    _chk(dcol, data, offset, grad_data, grad_offset)
+    kh, kw = _pair(kernel); sh, sw = _pair(stride); dh, dw = _pair(dilate); ph, pw = _pair(pad)
+    B, Cc, H, W = data.shape
+    assert offset.dtype == torch.float32 and dcol.stride(1) == 1 and dcol.shape[0] == B * offset.shape[2] * offset.shape[3]
+    if grad_data is None:
+        grad_data = torch.zeros((B, H, W, Cc), device=data.device, dtype=torch.float32).permute(0, 3, 1, 2)
+    if grad_offset is None:
+        grad_offset = torch.zeros((B, offset.shape[2], offset.shape[3], offset.shape[1]), device=data.device, dtype=torch.float32).permute(0, 3, 1, 2)
+    assert grad_data.dtype == torch.float32 and grad_offset.dtype == torch.float32
+    assert tuple(grad_data.shape) == tuple(data.shape) and tuple(grad_offset.shape) == tuple(offset.shape)
+    _lib.call('relnet_deformable_col2im', dcol.data_ptr(), dcol.stride(0), _dt(dcol), data.data_ptr(), _strides4(data), _dt(data),
+              offset.data_ptr(), _strides4(offset), grad_data.data_ptr(), _strides4(grad_data), grad_offset.data_ptr(), _strides4(grad_offset),
+              B, Cc, H, W, kh, kw, ph, pw, sh, sw, dh, dw, num_deformable_group, _stream())
+    return grad_data, grad_offset
+
+
 def deformable_conv_bwd(data, offset, w_packed, dy, kernel=(3, 3), stride=(1, 1), dilate=(1, 1), pad=(0, 0),
                         num_deformable_group=1, col=None):
     """Adjoint of deformable_conv.  data logical [B,C,H,W], offset fp32 logical [B,2*kh*kw*dg,Ho,Wo], dy logical
@@ -1638,8 +1659,6 @@ def deformable_conv_bwd(data, offset, w_packed, dy, kernel=(3, 3), stride=(1, 1)
     -> (grad_data fp32 [B,H,W,C] (NHWC), grad_offset fp32 [B,Ho,Wo,2*kh*kw*dg] (NHWC), grad_weight fp32 [Cout, kh*kw*C])."""
     from . import train_ops as T
     _chk(data, offset, w_packed, dy)
-    kh, kw = _pair(kernel); sh, sw = _pair(stride); dh, dw = _pair(dilate); ph, pw = _pair(pad)
-    B, Cc, H, W = data.shape
     Cout = w_packed.shape[0]
     dy2 = dy.permute(0, 2, 3, 1).reshape(-1, Cout)
     assert dy2.stride(1) == 1
@@ -1653,11 +1672,7 @@ def deformable_conv_bwd(data, offset, w_packed, dy, kernel=(3, 3), stride=(1, 1)
     # (bf16 layers: the column gradient is rounded to bf16 like every other data gradient of the bf16 trunk -- the gather form of col2im reads
     #  each of its rows ~4 times)
     dcol = gemm_nt(dyp, w_t, out_dtype=torch.float32 if data.dtype == torch.float32 else torch.bfloat16)
-    gdata = torch.zeros((B, H, W, Cc), device=data.device, dtype=torch.float32).permute(0, 3, 1, 2)
-    goff = torch.zeros((B, offset.shape[2], offset.shape[3], offset.shape[1]), device=data.device, dtype=torch.float32).permute(0, 3, 1, 2)
-    _lib.call('relnet_deformable_col2im', dcol.data_ptr(), dcol.stride(0), _dt(dcol), data.data_ptr(), _strides4(data), _dt(data),
-              offset.data_ptr(), _strides4(offset), gdata.data_ptr(), _strides4(gdata), goff.data_ptr(), _strides4(goff),
-              B, Cc, H, W, kh, kw, ph, pw, sh, sw, dh, dw, num_deformable_group, _stream())
+    gdata, goff = deformable_col2im(dcol, data, offset, kernel, stride, dilate, pad, num_deformable_group)
     if col is None or col.dtype != dy2.dtype:       # (col: the forward's column matrix, deformable_conv(want_col=True))
         col, _ = deformable_im2col(data, offset, kernel, stride, dilate, pad, num_deformable_group, col_dtype=dy2.dtype)
     gw = T.wgrad(dy2, col)

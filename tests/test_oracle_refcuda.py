@@ -11,6 +11,9 @@ deformable operators and of the CUDA NMS order:
     (asserted as a bound, not a pin);
   * `_nms`: identical keep lists, including duplicated boxes (IoU exactly 1), 64 / 65-box block boundaries and one box;
   * backward kernels (atomicAdd accumulation, order not deterministic): oracle/deform_torch.py's float64 autograd within 1e-5.
+    The non-smooth points these vectors leave open (the 3 % of the offset gradient excused below: samples exactly on an integer, on 0, H-1 or H,
+    in the clamp band) are pinned separately, bit for bit, by tests/golden/ref_cuda_deform_edges.npz: the same reference kernels on the exact
+    lattices of tests/deform_edge_cases.py (tests/test_deform_edge_cases_host.py, tests/test_gpu_deform_edges.py).
 """
 import os
 import sys
