@@ -298,6 +298,12 @@ int relnet_detect_head(const float* cls_score, long cs_ld, const float* bbox_pre
 int relnet_detect_head_ex(const float* cls_score, long cs_ld, const float* bbox_pred, long bp_ld, const float* rois,
                           const float* im_info, float* cls_prob, double* boxes, int R, int C, int rois_per_image,
                           int delta_off, const int* n_valid, void* stream);
+/* CLASS_AGNOSTIC false (tester.py:148-156 decodes every column of bbox_pred [R,4C], background included; :253 gives class j
+ * the columns 4j..4j+3): boxes [R,C,4] float64, the same arithmetic per class as relnet_detect_head_ex with delta_off = 4j.
+ * bp_ld >= 4C.  Padding rows (n_valid) get zeros for all C boxes.                                                          */
+int relnet_detect_head_cs(const float* cls_score, long cs_ld, const float* bbox_pred, long bp_ld, const float* rois,
+                          const float* im_info, float* cls_prob, double* boxes, int R, int C, int rois_per_image,
+                          const int* n_valid, void* stream);
 /* lib/nms/nms.py:85-141 soft_nms (soft != 0, nms_param = sigma) or :45-82 nms (nms_param = IoU
  * threshold), float64 like numpy; dets [B,C-1,N,5] in pick order, counts [B,C-1].                    */
 int relnet_class_nms(const float* cls_prob, const double* boxes, double* dets, int* counts, int B, int N, int C,
@@ -316,6 +322,12 @@ int relnet_class_nms_ex(const float* cls_prob, const double* scores64, const dou
 int relnet_class_nms_hist_bins(void);
 int relnet_class_nms_topk(const float* cls_prob, const double* boxes, double* dets, int* counts, void* hist, int B, int N, int C,
                           float score_thresh, double nms_param, int soft, int max_picks, int top_k, void* stream);
+/* CLASS_AGNOSTIC false (tester.py:253 `boxes[indexes, j*4:(j+1)*4]`): boxes [B,N,C,4] float64 (relnet_detect_head_cs), class j's
+ * candidates carry their own box.  Otherwise relnet_class_nms_ex (pick_index nullable) and relnet_class_nms_topk.          */
+int relnet_class_nms_cs(const float* cls_prob, const double* boxes, double* dets, int* counts, int* pick_index, int B, int N,
+                        int C, float score_thresh, double nms_param, int soft, int max_picks, void* stream);
+int relnet_class_nms_topk_cs(const float* cls_prob, const double* boxes, double* dets, int* counts, void* hist, int B, int N,
+                             int C, float score_thresh, double nms_param, int soft, int max_picks, int top_k, void* stream);
 /* tester.py:270-277: image threshold = max_per_image-th largest score; out [B,max_out,6] =
  * (class, score, x1, y1, x2, y2), class-major in pick order.                                        */
 int relnet_image_topk(const double* dets, const int* counts, double* thresh, int* total, float* out,
@@ -335,6 +347,15 @@ int relnet_lnms_prepare_ex(const float* cls_score, long cs_ld, const float* bbox
  * sorted_bbox [B,F,NC,4], class_boxes [B,NC,F,4], class_max [B,NC].  Ties: smaller roi index first.  */
 int relnet_lnms_sort(const float* prob, const float* boxes, int* rank_idx, float* sorted_score, float* sorted_bbox,
                      float* class_boxes, float* class_max, int B, int N, int NC, int first_n, void* stream);
+/* class_agnostic false (learn_nms.py:283-287: bbox_pred[:, 4:] viewed as [N,C-1,4], every foreground class refined from its own
+ * four columns; :311-321: after the per-class sort `pick` takes class c's box of roi idx[r,c]).  prepare_cs: boxes [B,N,C-1,4]
+ * float32, bp_ld >= 4C, means4 / stds4 / n_valid as relnet_lnms_prepare_ex.  sort_cs: the same outputs as relnet_lnms_sort from
+ * boxes [B,N,NC,4]: sorted_bbox[b,r,c] = boxes[b, rank_idx[b,c,r], c].                                                      */
+int relnet_lnms_prepare_cs(const float* cls_score, long cs_ld, const float* bbox_pred, long bp_ld, const float* rois,
+                           const float* im_info, float* prob /*[B,N,C-1]*/, float* boxes /*[B,N,C-1,4]*/, int B, int N, int C,
+                           const float* means4, const float* stds4, const int* n_valid, void* stream);
+int relnet_lnms_sort_cs(const float* prob, const float* boxes, int* rank_idx, float* sorted_score, float* sorted_bbox,
+                        float* class_boxes, float* class_max, int B, int N, int NC, int first_n, void* stream);
 /* :335-344: x[b,c,r,:] = roi_feat_embedding[b, rank_idx[b,c,r], :] + rank_feat[r, :]                    */
 int relnet_lnms_embed(const void* roi_emb, const float* rank_feat, const int* rank_idx, void* x, int B, int N,
                       int NC, int first_n, int D, int dtype, void* stream);

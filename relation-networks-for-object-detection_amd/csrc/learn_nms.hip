@@ -5,6 +5,7 @@
 // here the valid-class rule is evaluated on device and invalid classes simply produce zeros.
 //
 //   lnms_prepare_kernel   softmax over classes + refine_bbox_nd (:175-217) + clip, float32
+//   lnms_prepare_cs_kernel  the same with every foreground class refined from its own four columns (class_agnostic false, :283-287)
 //   lnms_sort_kernel      per (image, class): descending sort of the N scores, first_n ranks,
 //                         gathers sorted_score / sorted_bbox (:289-308)
 //   lnms_embed_kernel     X[b,c,r,:] = roi_feat_embedding[idx[r,c]] + rank_feat[r]  (:335-344)
@@ -23,13 +24,42 @@ struct PrepArgs {
   const float* rois;                    // [B*N, 5]
   const float* im_info;                 // [B, 3]
   float* prob;                          // [B*N, C-1]  (background dropped)
-  float* boxes;                         // [B*N, 4]    refined + clipped
+  float* boxes;                         // [B*N, 4]    refined + clipped ([B*N, C-1, 4]: lnms_prepare_cs_kernel)
   int C, N, delta_off;
   float m0, m1, m2, m3, s0, s1, s2, s3; // bbox means / stds (0/1 when the graph passes None)
   const int* n_valid;                   // optional [B]: rows past n_valid[b] are padding -> probability 0 (they sort last)
 };
 
 #pragma clang fp contract(off)
+// One wavefront: prob[c - 1] = softmax(z)[c] for the foreground classes c = 1..C-1.
+__device__ __forceinline__ void softmax_row_fg(const float* z, float* prob, int C, int lane) {
+  float m = -INFINITY;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += expf(z[c] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  for (int c = lane + 1; c < C; c += 64) prob[c - 1] = expf(z[c] - m) / s;
+}
+
+// refine_bbox_nd (learn_nms.py:175-217) of ONE box in float32: roi [5], d = its four deltas, info = the image's (h, w, scale).
+__device__ __forceinline__ float4 refine_box(const PrepArgs& g, const float* roi, const float* d, const float* info) {
+  const float x1 = roi[1], y1 = roi[2], x2 = roi[3], y2 = roi[4];
+  const float w = x2 - x1 + 1.f, h = y2 - y1 + 1.f;
+  const float cx = 0.5f * (x1 + x2), cy = 0.5f * (y1 + y2);
+  const float dx = d[0] * g.s0 + g.m0, dy = d[1] * g.s1 + g.m1, dw = d[2] * g.s2 + g.m2, dh = d[3] * g.s3 + g.m3;
+  const float rcx = cx + w * dx, rcy = cy + h * dy;
+  const float rw = w * (float)exp((double)dw), rh = h * (float)exp((double)dh);
+  const float wo = 0.5f * (rw - 1.f), ho = 0.5f * (rh - 1.f);
+  const float mx = info[1] - 1.f, my = info[0] - 1.f;
+  float o[4] = {rcx - wo, rcy - ho, rcx + wo, rcy + ho};
+  o[0] = fmaxf(fminf(o[0], mx), 0.f); o[1] = fmaxf(fminf(o[1], my), 0.f);
+  o[2] = fmaxf(fminf(o[2], mx), 0.f); o[3] = fmaxf(fminf(o[3], my), 0.f);
+  return make_float4(o[0], o[1], o[2], o[3]);
+}
+
 __global__ __launch_bounds__(64) void lnms_prepare_kernel(PrepArgs g) {
   const int r = blockIdx.x, lane = threadIdx.x;
   if (g.n_valid && (r % g.N) >= g.n_valid[r / g.N]) {
@@ -37,33 +67,28 @@ __global__ __launch_bounds__(64) void lnms_prepare_kernel(PrepArgs g) {
     if (lane == 0) *(float4*)(g.boxes + (long)r * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
-  const float* z = g.cls_score + (long)r * g.cs_ld;
-  float m = -INFINITY;
-  for (int c = lane; c < g.C; c += 64) m = fmaxf(m, z[c]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f;
-  for (int c = lane; c < g.C; c += 64) s += expf(z[c] - m);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  for (int c = lane + 1; c < g.C; c += 64) g.prob[(long)r * (g.C - 1) + c - 1] = expf(z[c] - m) / s;
-  if (lane == 0) {
-    const float* roi = g.rois + (long)r * 5;
-    const float* d = g.bbox_pred + (long)r * g.bp_ld + g.delta_off;
-    const float* info = g.im_info + (long)(r / g.N) * 3;
-    const float x1 = roi[1], y1 = roi[2], x2 = roi[3], y2 = roi[4];
-    const float w = x2 - x1 + 1.f, h = y2 - y1 + 1.f;
-    const float cx = 0.5f * (x1 + x2), cy = 0.5f * (y1 + y2);
-    const float dx = d[0] * g.s0 + g.m0, dy = d[1] * g.s1 + g.m1, dw = d[2] * g.s2 + g.m2, dh = d[3] * g.s3 + g.m3;
-    const float rcx = cx + w * dx, rcy = cy + h * dy;
-    const float rw = w * (float)exp((double)dw), rh = h * (float)exp((double)dh);
-    const float wo = 0.5f * (rw - 1.f), ho = 0.5f * (rh - 1.f);
-    const float mx = info[1] - 1.f, my = info[0] - 1.f;
-    float o[4] = {rcx - wo, rcy - ho, rcx + wo, rcy + ho};
-    o[0] = fmaxf(fminf(o[0], mx), 0.f); o[1] = fmaxf(fminf(o[1], my), 0.f);
-    o[2] = fmaxf(fminf(o[2], mx), 0.f); o[3] = fmaxf(fminf(o[3], my), 0.f);
-    *(float4*)(g.boxes + (long)r * 4) = make_float4(o[0], o[1], o[2], o[3]);
+  softmax_row_fg(g.cls_score + (long)r * g.cs_ld, g.prob + (long)r * (g.C - 1), g.C, lane);
+  if (lane == 0)
+    *(float4*)(g.boxes + (long)r * 4) = refine_box(g, g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + g.delta_off,
+                                                   g.im_info + (long)(r / g.N) * 3);
+}
+
+// Class-specific form (class_agnostic false, learn_nms.py:283-287): bbox_pred[:, 4:] is [N, C-1, 4], foreground class k is refined from
+// its own columns 4 (k + 1)..4 (k + 1) + 3 -> boxes [B*N, C-1, 4].  One foreground class per lane.
+__global__ __launch_bounds__(64) void lnms_prepare_cs_kernel(PrepArgs g) {
+  const int r = blockIdx.x, lane = threadIdx.x, NC = g.C - 1;
+  float* out = g.boxes + (long)r * NC * 4;
+  if (g.n_valid && (r % g.N) >= g.n_valid[r / g.N]) {
+    for (int k = lane; k < NC; k += 64) {
+      g.prob[(long)r * NC + k] = 0.f;
+      *(float4*)(out + 4 * k) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
   }
+  softmax_row_fg(g.cls_score + (long)r * g.cs_ld, g.prob + (long)r * NC, g.C, lane);
+  for (int k = lane; k < NC; k += 64)
+    *(float4*)(out + 4 * k) = refine_box(g, g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + 4 * (k + 1),
+                                         g.im_info + (long)(r / g.N) * 3);
 }
 #pragma clang fp contract(fast)
 
@@ -74,13 +99,14 @@ __device__ __forceinline__ unsigned int fkey32(float f) {
 
 struct SortArgs {
   const float* prob;      // [B, N, NC]
-  const float* boxes;     // [B, N, 4]
+  const float* boxes;     // roi i of image b, class c: boxes + (b N + i) box_row_stride + c box_cls_stride ([B, N, 4]: 4, 0; [B, N, NC, 4]: 4 NC, 4)
   int* rank_idx;          // [B, NC, F]
   float* sorted_score;    // [B, F, NC]
   float* sorted_bbox;     // [B, F, NC, 4]
   float* class_boxes;     // [B, NC, F, 4]   (class-major copy: "images" of the geometry kernel)
   float* class_max;       // [B, NC]
   int N, NC, F;
+  int box_row_stride, box_cls_stride;     // in floats, multiples of 4 (float4 loads)
 };
 
 // One workgroup per (class, image); N <= 1024.  Ties: smaller roi index first.
@@ -110,7 +136,7 @@ __global__ __launch_bounds__(256) void lnms_sort_kernel(SortArgs g) {
   for (int r = tid; r < g.F; r += 256) {
     const int idx = 0xffff - (int)(keys[r] & 0xffffu);
     const float s = g.prob[((long)b * g.N + idx) * g.NC + c];
-    const float4 bx = *(const float4*)(g.boxes + ((long)b * g.N + idx) * 4);
+    const float4 bx = *(const float4*)(g.boxes + ((long)b * g.N + idx) * g.box_row_stride + (long)c * g.box_cls_stride);
     g.rank_idx[((long)b * g.NC + c) * g.F + r] = idx;
     g.sorted_score[((long)b * g.F + r) * g.NC + c] = s;
     *(float4*)(g.sorted_bbox + (((long)b * g.F + r) * g.NC + c) * 4) = bx;
@@ -267,14 +293,42 @@ extern "C" int relnet_lnms_prepare(const float* cls_score, long cs_ld, const flo
                                 stds4, nullptr, stream);
 }
 
+extern "C" int relnet_lnms_prepare_cs(const float* cls_score, long cs_ld, const float* bbox_pred, long bp_ld, const float* rois,
+                                      const float* im_info, float* prob, float* boxes, int B, int N, int C, const float* means4,
+                                      const float* stds4, const int* n_valid, void* stream) {
+  RELNET_REQUIRE(cls_score && bbox_pred && rois && im_info && prob && boxes, "relnet_lnms_prepare_cs: null operand");
+  RELNET_REQUIRE(B > 0 && N > 0 && C > 1, "relnet_lnms_prepare_cs: bad shape");
+  RELNET_REQUIRE(bp_ld >= 4L * C, "relnet_lnms_prepare_cs: bbox_pred rows hold %ld deltas, 4 per class needs %d", bp_ld, 4 * C);
+  PrepArgs g{cls_score, cs_ld, bbox_pred, bp_ld, rois, im_info, prob, boxes, C, N, 0,
+             means4 ? means4[0] : 0.f, means4 ? means4[1] : 0.f, means4 ? means4[2] : 0.f, means4 ? means4[3] : 0.f,
+             stds4 ? stds4[0] : 1.f, stds4 ? stds4[1] : 1.f, stds4 ? stds4[2] : 1.f, stds4 ? stds4[3] : 1.f, n_valid};
+  lnms_prepare_cs_kernel<<<B * N, 64, 0, (hipStream_t)stream>>>(g);
+  return check_launch("relnet_lnms_prepare_cs");
+}
+
+static int lnms_sort_launch(const char* name, const float* prob, const float* boxes, int* rank_idx, float* sorted_score,
+                            float* sorted_bbox, float* class_boxes, float* class_max, int B, int N, int NC, int first_n,
+                            int box_row_stride, int box_cls_stride, void* stream) {
+  RELNET_REQUIRE(prob && boxes && rank_idx && sorted_score && sorted_bbox && class_boxes && class_max, "%s: null operand", name);
+  RELNET_REQUIRE(B > 0 && N > 0 && N <= 1024 && NC > 0 && first_n > 0 && first_n <= N, "%s: need first_n <= N <= 1024", name);
+  SortArgs g{prob, boxes, rank_idx, sorted_score, sorted_bbox, class_boxes, class_max, N, NC, first_n, box_row_stride, box_cls_stride};
+  lnms_sort_kernel<<<dim3(NC, B), 256, 0, (hipStream_t)stream>>>(g);
+  return check_launch(name);
+}
+
 extern "C" int relnet_lnms_sort(const float* prob, const float* boxes, int* rank_idx, float* sorted_score,
                                 float* sorted_bbox, float* class_boxes, float* class_max, int B, int N, int NC,
                                 int first_n, void* stream) {
-  RELNET_REQUIRE(prob && boxes && rank_idx && sorted_score && sorted_bbox && class_boxes && class_max, "relnet_lnms_sort: null operand");
-  RELNET_REQUIRE(B > 0 && N > 0 && N <= 1024 && NC > 0 && first_n > 0 && first_n <= N, "relnet_lnms_sort: need first_n <= N <= 1024");
-  SortArgs g{prob, boxes, rank_idx, sorted_score, sorted_bbox, class_boxes, class_max, N, NC, first_n};
-  lnms_sort_kernel<<<dim3(NC, B), 256, 0, (hipStream_t)stream>>>(g);
-  return check_launch("relnet_lnms_sort");
+  return lnms_sort_launch("relnet_lnms_sort", prob, boxes, rank_idx, sorted_score, sorted_bbox, class_boxes, class_max, B, N, NC, first_n,
+                          4, 0, stream);
+}
+
+// boxes [B, N, NC, 4] (relnet_lnms_prepare_cs): sorted_bbox[r, c] = boxes[idx[r, c], c] (the `pick` of learn_nms.py:311-321).
+extern "C" int relnet_lnms_sort_cs(const float* prob, const float* boxes, int* rank_idx, float* sorted_score,
+                                   float* sorted_bbox, float* class_boxes, float* class_max, int B, int N, int NC,
+                                   int first_n, void* stream) {
+  return lnms_sort_launch("relnet_lnms_sort_cs", prob, boxes, rank_idx, sorted_score, sorted_bbox, class_boxes, class_max, B, N, NC,
+                          first_n, 4 * NC, 4, stream);
 }
 
 extern "C" int relnet_lnms_embed(const void* roi_emb, const float* rank_feat, const int* rank_idx, void* x, int B,

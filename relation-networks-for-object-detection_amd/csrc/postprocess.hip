@@ -5,6 +5,7 @@
 //
 //   detect_head_kernel      softmax over classes (SoftmaxActivation) + class-agnostic box
 //                           decode (bbox_transform.py:103-140, float64) + clip + 1/scale.
+//   detect_head_cs_kernel   the same with one decoded box PER CLASS (CLASS_AGNOSTIC false: bbox_pred [R, 4 C], tester.py:253).
 //   class_nms_kernel        per (image, class): candidates with prob > thresh, then Gaussian
 //                           soft-NMS (score *= exp(-iou^2/sigma), re-pick the max each step) or
 //                           greedy NMS (drop iou > thresh); all arithmetic float64 like numpy.
@@ -19,12 +20,41 @@ struct HeadArgs {
   const float* rois;                      // [R, 5]
   const float* im_info;                   // [B, 3]
   float* cls_prob;                        // [R, C]
-  double* boxes;                          // [R, 4] decoded, clipped, divided by im scale
-  int R, C, rois_per_image, delta_off;
+  double* boxes;                          // [R, 4] decoded, clipped, divided by im scale ([R, C, 4]: detect_head_cs_kernel)
+  int R, C, rois_per_image, delta_off;    // (delta_off: detect_head_kernel only)
   const int* n_valid;                     // optional [B]: rows past n_valid[b] of image b are padding -> all-zero outputs
 };
 
 #pragma clang fp contract(off)
+// One wavefront: cls_prob[c] = softmax(z)[c] over C classes.
+__device__ __forceinline__ void softmax_row(const float* z, float* prob, int C, int lane) {
+  float m = -INFINITY;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += expf(z[c] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  for (int c = lane; c < C; c += 64) prob[c] = expf(z[c] - m) / s;
+}
+
+// bbox_pred (bbox_transform.py:103-140, float64 on float32 deltas, exp rounded to float32 like numpy) + clip_boxes + 1 / scale
+// of ONE box: roi [5], d = its four deltas, info = the image's (h, w, scale).
+__device__ __forceinline__ void decode_box(const float* roi, const float* d, const float* info, double o[4]) {
+  const double x1 = roi[1], y1 = roi[2], x2 = roi[3], y2 = roi[4];
+  const double w = x2 - x1 + 1.0, h = y2 - y1 + 1.0;
+  const double cx = x1 + 0.5 * (w - 1.0), cy = y1 + 0.5 * (h - 1.0);
+  const double pcx = (double)d[0] * w + cx, pcy = (double)d[1] * h + cy;
+  const double pw = (double)(float)exp((double)d[2]) * w, ph = (double)(float)exp((double)d[3]) * h;
+  const double mx = (double)info[1] - 1.0, my = (double)info[0] - 1.0, sc = (double)info[2];
+  o[0] = pcx - 0.5 * (pw - 1.0); o[1] = pcy - 0.5 * (ph - 1.0); o[2] = pcx + 0.5 * (pw - 1.0); o[3] = pcy + 0.5 * (ph - 1.0);
+  o[0] = fmax(fmin(o[0], mx), 0.0); o[1] = fmax(fmin(o[1], my), 0.0);
+  o[2] = fmax(fmin(o[2], mx), 0.0); o[3] = fmax(fmin(o[3], my), 0.0);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) o[c] = o[c] / sc;
+}
+
 __global__ __launch_bounds__(64) void detect_head_kernel(HeadArgs g) {
   const int r = blockIdx.x, lane = threadIdx.x;
   if (g.n_valid && (r % g.rois_per_image) >= g.n_valid[r / g.rois_per_image]) {     // padding row: never a detection
@@ -32,38 +62,38 @@ __global__ __launch_bounds__(64) void detect_head_kernel(HeadArgs g) {
     if (lane < 4) g.boxes[(long)r * 4 + lane] = 0.0;
     return;
   }
-  const float* z = g.cls_score + (long)r * g.cs_ld;
-  float m = -INFINITY;
-  for (int c = lane; c < g.C; c += 64) m = fmaxf(m, z[c]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f;
-  for (int c = lane; c < g.C; c += 64) s += expf(z[c] - m);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  for (int c = lane; c < g.C; c += 64) g.cls_prob[(long)r * g.C + c] = expf(z[c] - m) / s;
+  softmax_row(g.cls_score + (long)r * g.cs_ld, g.cls_prob + (long)r * g.C, g.C, lane);
   if (lane == 0) {
-    const float* roi = g.rois + (long)r * 5;
-    const float* d = g.bbox_pred + (long)r * g.bp_ld + g.delta_off;
-    const float* info = g.im_info + (long)(r / g.rois_per_image) * 3;
-    const double x1 = roi[1], y1 = roi[2], x2 = roi[3], y2 = roi[4];
-    const double w = x2 - x1 + 1.0, h = y2 - y1 + 1.0;
-    const double cx = x1 + 0.5 * (w - 1.0), cy = y1 + 0.5 * (h - 1.0);
-    const double pcx = (double)d[0] * w + cx, pcy = (double)d[1] * h + cy;
-    const double pw = (double)(float)exp((double)d[2]) * w, ph = (double)(float)exp((double)d[3]) * h;
-    const double mx = (double)info[1] - 1.0, my = (double)info[0] - 1.0, sc = (double)info[2];
-    double o[4] = {pcx - 0.5 * (pw - 1.0), pcy - 0.5 * (ph - 1.0), pcx + 0.5 * (pw - 1.0), pcy + 0.5 * (ph - 1.0)};
-    o[0] = fmax(fmin(o[0], mx), 0.0); o[1] = fmax(fmin(o[1], my), 0.0);
-    o[2] = fmax(fmin(o[2], mx), 0.0); o[3] = fmax(fmin(o[3], my), 0.0);
+    double o[4];
+    decode_box(g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + g.delta_off, g.im_info + (long)(r / g.rois_per_image) * 3, o);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) g.boxes[(long)r * 4 + c] = o[c] / sc;
+    for (int c = 0; c < 4; ++c) g.boxes[(long)r * 4 + c] = o[c];
+  }
+}
+
+// Class-specific form (CLASS_AGNOSTIC false: tester.py:148-156 decodes all 4 C columns, :253 hands class j the columns 4j..4j+3):
+// boxes [R, C, 4], background included.  Same softmax; the decode runs one class per lane instead of on lane 0.
+__global__ __launch_bounds__(64) void detect_head_cs_kernel(HeadArgs g) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  double* out = g.boxes + (long)r * g.C * 4;
+  if (g.n_valid && (r % g.rois_per_image) >= g.n_valid[r / g.rois_per_image]) {
+    for (int c = lane; c < g.C; c += 64) g.cls_prob[(long)r * g.C + c] = 0.f;
+    for (int k = lane; k < 4 * g.C; k += 64) out[k] = 0.0;
+    return;
+  }
+  softmax_row(g.cls_score + (long)r * g.cs_ld, g.cls_prob + (long)r * g.C, g.C, lane);
+  for (int c = lane; c < g.C; c += 64) {
+    double o[4];
+    decode_box(g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + 4 * c, g.im_info + (long)(r / g.rois_per_image) * 3, o);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[4 * c + k] = o[k];
   }
 }
 
 // ---------------------------------------------------------------------------------------
 struct ClsNmsArgs {
   const float* cls_prob;     // [B, N, C]
-  const double* boxes;       // [B, N, 4]
+  const double* boxes;       // roi i of image b, class cls: boxes + (b N + i) box_row_stride + cls box_cls_stride ([B, N, 4]: 4, 0; [B, N, C, 4]: 4 C, 4)
   double* dets;              // [B, C-1, N, 5]  x1,y1,x2,y2,score in pick order
   int* counts;               // [B, C-1]
   int N, C;
@@ -78,6 +108,7 @@ struct ClsNmsArgs {
   int* pick_index;           // optional [B, C-1, N]: roi index of every pick (`keep` of nms.py:45-82)
   unsigned int* hist;        // PRUNE kernels: [B, kHistBins] zero-initialised by the caller: histogram of the keys of all picks of an image
   int top_k;                 // PRUNE kernels: max_per_image
+  int box_row_stride, box_cls_stride;     // in doubles
 };
 
 // Image-level pruning of the per-class lists (tester.py:270-277 keeps, per image, the detections whose score is >= the top_k-th
@@ -172,7 +203,7 @@ __global__ __launch_bounds__(64 * WAVES) void class_nms_kernel(ClsNmsArgs g) {
     if (i < g.N) {
       const double p = g.scores64 ? g.scores64[(long)b * g.N + i] : (double)g.cls_prob[((long)b * g.N + i) * g.C + cls];
       if (p > (double)g.score_thresh) {
-        const double* bx = g.boxes + ((long)b * g.N + i) * 4;
+        const double* bx = g.boxes + ((long)b * g.N + i) * g.box_row_stride + (long)cls * g.box_cls_stride;
         sc[s] = p;
         x1[s] = bx[0]; y1[s] = bx[1]; x2[s] = bx[2]; y2[s] = bx[3];
         area[s] = (x2[s] - x1[s] + 1) * (y2[s] - y1[s] + 1);
@@ -497,6 +528,17 @@ extern "C" int relnet_detect_head(const float* cls_score, long cs_ld, const floa
                                delta_off, nullptr, stream);
 }
 
+extern "C" int relnet_detect_head_cs(const float* cls_score, long cs_ld, const float* bbox_pred, long bp_ld, const float* rois,
+                                     const float* im_info, float* cls_prob, double* boxes, int R, int C, int rois_per_image,
+                                     const int* n_valid, void* stream) {
+  RELNET_REQUIRE(cls_score && bbox_pred && rois && im_info && cls_prob && boxes, "relnet_detect_head_cs: null operand");
+  RELNET_REQUIRE(R > 0 && C > 1 && rois_per_image > 0, "relnet_detect_head_cs: bad shape");
+  RELNET_REQUIRE(bp_ld >= 4L * C, "relnet_detect_head_cs: bbox_pred rows hold %ld deltas, 4 per class needs %d", bp_ld, 4 * C);
+  HeadArgs g{cls_score, cs_ld, bbox_pred, bp_ld, rois, im_info, cls_prob, boxes, R, C, rois_per_image, 0, n_valid};
+  detect_head_cs_kernel<<<R, 64, 0, (hipStream_t)stream>>>(g);
+  return check_launch("relnet_detect_head_cs");
+}
+
 // One candidate per thread, the smallest workgroup that holds N of them (300 rois: 5 waves; FPN's 1000 + 4: 16).  (The one-wave form --
 // N / 64 candidates per lane, half the instructions per pick -- was kept for launches of >= 1536 (image, class) pairs at first: faster
 // in isolation at 54 images, 206 vs 242 us, but inside the step the multi-wave form wins or ties at every batch size, 19.19 vs
@@ -518,9 +560,20 @@ extern "C" int relnet_class_nms_ex(const float* cls_prob, const double* scores64
   RELNET_REQUIRE(B > 0 && N > 0 && N <= 1024 && C > 1, "relnet_class_nms: need 0 < N <= 1024 (N=%d)", N);
   RELNET_REQUIRE(!scores64 || C == 2, "relnet_class_nms: float64 scores are one foreground class (C == 2), got C=%d", C);
   ClsNmsArgs g{cls_prob, boxes, dets, counts, N, C, score_thresh, nms_param, soft, max_picks > 0 ? max_picks : N,
-               scores64, pick_index, nullptr, 0};
+               scores64, pick_index, nullptr, 0, 4, 0};
   launch_class_nms<false>(g, B, (hipStream_t)stream);
   return check_launch("relnet_class_nms");
+}
+
+// Class-specific boxes [B, N, C, 4] (relnet_detect_head_cs): class j's candidates carry the box at columns 4j..4j+3 (tester.py:253).
+extern "C" int relnet_class_nms_cs(const float* cls_prob, const double* boxes, double* dets, int* counts, int* pick_index, int B,
+                                   int N, int C, float score_thresh, double nms_param, int soft, int max_picks, void* stream) {
+  RELNET_REQUIRE(cls_prob && boxes && dets && counts, "relnet_class_nms_cs: null operand");
+  RELNET_REQUIRE(B > 0 && N > 0 && N <= 1024 && C > 1, "relnet_class_nms_cs: need 0 < N <= 1024 (N=%d)", N);
+  ClsNmsArgs g{cls_prob, boxes, dets, counts, N, C, score_thresh, nms_param, soft, max_picks > 0 ? max_picks : N,
+               nullptr, pick_index, nullptr, 0, 4 * C, 4};
+  launch_class_nms<false>(g, B, (hipStream_t)stream);
+  return check_launch("relnet_class_nms_cs");
 }
 
 extern "C" int relnet_class_nms(const float* cls_prob, const double* boxes, double* dets, int* counts,
@@ -539,9 +592,19 @@ extern "C" int relnet_class_nms_topk(const float* cls_prob, const double* boxes,
   RELNET_REQUIRE(cls_prob && boxes && dets && counts && hist, "relnet_class_nms_topk: null operand");
   RELNET_REQUIRE(B > 0 && N > 0 && N <= 1024 && C > 1 && top_k > 0, "relnet_class_nms_topk: need 0 < N <= 1024, top_k > 0 (N=%d top_k=%d)", N, top_k);
   ClsNmsArgs g{cls_prob, boxes, dets, counts, N, C, score_thresh, nms_param, soft, max_picks > 0 ? max_picks : N, nullptr, nullptr,
-               (unsigned int*)hist, top_k};
+               (unsigned int*)hist, top_k, 4, 0};
   launch_class_nms<true>(g, B, (hipStream_t)stream);
   return check_launch("relnet_class_nms_topk");
+}
+
+extern "C" int relnet_class_nms_topk_cs(const float* cls_prob, const double* boxes, double* dets, int* counts, void* hist, int B, int N,
+                                        int C, float score_thresh, double nms_param, int soft, int max_picks, int top_k, void* stream) {
+  RELNET_REQUIRE(cls_prob && boxes && dets && counts && hist, "relnet_class_nms_topk_cs: null operand");
+  RELNET_REQUIRE(B > 0 && N > 0 && N <= 1024 && C > 1 && top_k > 0, "relnet_class_nms_topk_cs: need 0 < N <= 1024, top_k > 0 (N=%d top_k=%d)", N, top_k);
+  ClsNmsArgs g{cls_prob, boxes, dets, counts, N, C, score_thresh, nms_param, soft, max_picks > 0 ? max_picks : N, nullptr, nullptr,
+               (unsigned int*)hist, top_k, 4 * C, 4};
+  launch_class_nms<true>(g, B, (hipStream_t)stream);
+  return check_launch("relnet_class_nms_topk_cs");
 }
 
 extern "C" int relnet_image_topk(const double* dets, const int* counts, double* thresh, int* total,

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void proposal_target_kernel(PTArgs g) {
     }
     lab = gtb[bi * 5 + 4];
     if (best < (double)g.bg_thresh_hi) lab = 0.f;                      // rcnn.py:309-310
-    if (lab > 0.f) {
+    if (lab > 0.f && (g.class_agnostic || (int)lab < g.num_reg)) {      // (class-specific: a label past num_reg has no columns to write)
       // bbox_transform.py:74-100 on float32 arrays (numpy keeps float32), log correctly rounded
       const float* q = gtb + bi * 5;
       const float ew = box[2] - box[0] + 1.0f, eh = box[3] - box[1] + 1.0f;

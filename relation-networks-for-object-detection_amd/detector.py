@@ -42,6 +42,8 @@ class Config(object):
     roi_align = False         # True: ROIAlign (sampling_ratio 2) feeds fc_new_1 / roi_pool_fc1 instead of the graphs' ROIPooling -- the operator
     roi_align_sampling = 2    # north_star names; no reference graph uses it (SYM_REL:252-253 is ROIPooling), so it is off by default.  The C4 and
                               # FPN detectors and trainers honour it; with `dcn` (deformable PSROI pooling) it has no meaning and is refused
+    class_agnostic = True     # CLASS_AGNOSTIC.  False: bbox_pred is [*, 4 * num_classes], class j's boxes come from its columns 4j..4j+3
+                              # (symbols/...:157 num_reg_classes, core/tester.py:253, operator_py/learn_nms.py:283-287,311-321)
     pixel_means = PIXEL_MEANS  # network.PIXEL_MEANS (BGR): subtracted on the device when the detector is given uint8 images
 
     @classmethod
@@ -60,6 +62,7 @@ class Config(object):
         c.pixel_means = tuple(float(v) for v in n.PIXEL_MEANS)
         c.anchor_scales, c.anchor_ratios = tuple(n.ANCHOR_SCALES), tuple(n.ANCHOR_RATIOS)
         c.num_classes = e.dataset.NUM_CLASSES
+        c.class_agnostic = bool(e.CLASS_AGNOSTIC)
         c.nms_target_thresh = tuple(float(v) for v in str(n.NMS_TARGET_THRESH).split(','))
         src = t if train else te
         c.rpn_pre_nms_top_n, c.rpn_post_nms_top_n = src.RPN_PRE_NMS_TOP_N, src.RPN_POST_NMS_TOP_N
@@ -102,11 +105,25 @@ def check_pooling(cfg):
         raise ValueError("roi_align and dcn cannot be combined: the DCN graph pools with deformable PSROI pooling")
 
 
+def check_box_regression(cfg, params):
+    """bbox_pred_weight and cfg.class_agnostic must agree: 4 * num_classes rows are a class-specific head (num_reg_classes = num_classes,
+    symbols/...:157), anything else the class-agnostic one (8 rows; with num_classes == 2 the two layouts coincide).  A class-specific
+    checkpoint decoded as class-agnostic would give every class the box of class 1 without any error."""
+    rows = int(params['bbox_pred_weight'].shape[0])
+    specific = rows == 4 * cfg.num_classes and cfg.num_classes != 2
+    if specific and cfg.class_agnostic:
+        raise ValueError("bbox_pred_weight has 4 * num_classes = %d rows (a class-specific head) but cfg.class_agnostic is True" % rows)
+    if not cfg.class_agnostic and rows != 4 * cfg.num_classes:
+        raise ValueError("cfg.class_agnostic is False but bbox_pred_weight has %d rows, not 4 * num_classes = %d"
+                         % (rows, 4 * cfg.num_classes))
+
+
 class Detector(object):
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', cfg=None, relation=True,
                  im_hw=(600, 1000), stem='hip'):
         self.cfg = cfg or Config()
         check_pooling(self.cfg)
+        check_box_regression(self.cfg, params)
         self.dtype, self.device, self.relation, self.im_hw = dtype, device, relation, im_hw
         self.overlap_rpn = True
         # RPN head + proposal beside res5 on a side stream: under hipGraph capture the fork / join are graph edges and it pays from one
@@ -124,7 +141,8 @@ class Detector(object):
         if self.cfg.learn_nms:
             self.lnms = LearnNMS(params, self.cfg.num_classes - 1, self.cfg.first_n, len(self.cfg.nms_target_thresh),
                                  self.cfg.learn_nms_class_thresh, None, None, self.cfg.merge_method,
-                                 self.cfg.score_thresh, self.cfg.max_per_image, dtype=dtype, device=device)
+                                 self.cfg.score_thresh, self.cfg.max_per_image, dtype=dtype, device=device,
+                                 class_agnostic=self.cfg.class_agnostic)
         self.anchors = torch.as_tensor(generate_anchors(self.cfg.feat_stride, self.cfg.anchor_ratios,
                                                         self.cfg.anchor_scales), dtype=torch.float64, device=device)
 
@@ -187,8 +205,8 @@ class Detector(object):
             out.update(self.lnms.forward(cls_score.contiguous(), bbox_pred.contiguous(), rois, im_info, feat))
             return out
         prob, boxes = ops.detect_head(cls_score.reshape(B * N, -1), bbox_pred.reshape(B * N, -1),
-                                      rois.view(B * N, 5), im_info, N)
-        out['cls_prob'], out['pred_boxes'] = prob.view(B, N, -1), boxes.view(B, N, 4)
+                                      rois.view(B * N, 5), im_info, N, class_agnostic=c.class_agnostic)
+        out['cls_prob'], out['pred_boxes'] = prob.view(B, N, -1), boxes.view((B, N) + tuple(boxes.shape[1:]))       # [B,N,4], or [B,N,C,4] class-specific
         if post:
             # (top_k: a class list stops once its next pick cannot reach the image's max_per_image best scores -- the lists are
             #  prefixes of the full per-class lists that contain everything image_topk keeps: relnet_class_nms_topk)
@@ -272,6 +290,7 @@ class FPNDetector(object):
 
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', cfg=None, relation=True, stem='hip'):
         self.cfg = cfg or Config()
+        check_box_regression(self.cfg, params)
         self.dtype, self.device = dtype, device
         self.backbone = Backbone(params, dtype, device, stem=stem, fpn=True, pixel_means=self.cfg.pixel_means)
         self.head = RelationHead(params, dtype, device, fc1_perm=fc1_channels_last_perm(), use_relation=relation,
@@ -280,7 +299,8 @@ class FPNDetector(object):
         if self.cfg.learn_nms:
             self.lnms = LearnNMS(params, self.cfg.num_classes - 1, self.cfg.first_n, len(self.cfg.nms_target_thresh),
                                  self.cfg.learn_nms_class_thresh, None, None, self.cfg.merge_method,
-                                 self.cfg.score_thresh, self.cfg.max_per_image, dtype=dtype, device=device)
+                                 self.cfg.score_thresh, self.cfg.max_per_image, dtype=dtype, device=device,
+                                 class_agnostic=self.cfg.class_agnostic)
 
     pad_empty_levels = True
 
@@ -313,8 +333,8 @@ class FPNDetector(object):
             out.update(self.lnms.forward(cls_score.contiguous(), bbox_pred.contiguous(), rois, im_info, feat, n_valid=n_rows))
             return out
         prob, boxes = ops.detect_head(cls_score.reshape(B * N, -1), bbox_pred.reshape(B * N, -1),
-                                      rois.view(B * N, 5), im_info, N, n_valid=n_rows)
-        out['cls_prob'], out['pred_boxes'] = prob.view(B, N, -1), boxes.view(B, N, 4)
+                                      rois.view(B * N, 5), im_info, N, n_valid=n_rows, class_agnostic=c.class_agnostic)
+        out['cls_prob'], out['pred_boxes'] = prob.view(B, N, -1), boxes.view((B, N) + tuple(boxes.shape[1:]))
         if post:
             dets, cnts = ops.class_nms(out['cls_prob'], out['pred_boxes'], c.score_thresh, c.nms, c.softnms,
                                        max_picks=c.max_per_image, top_k=c.max_per_image)

@@ -26,10 +26,12 @@ def rank_embedding(rank_dim, feat_dim=1024, wave_length=1000.0):
 class LearnNMS(object):
     def __init__(self, params, num_fg_classes=80, first_n=100, num_thresh=5, class_thresh=0.01,
                  bbox_means=None, bbox_stds=None, merge_method=-1, score_thresh=1e-3, max_per_image=100,
-                 dtype=torch.bfloat16, device='cuda'):
+                 dtype=torch.bfloat16, device='cuda', class_agnostic=True):
+        """class_agnostic=False: bbox_pred is [B,N,4*(C+1)] and foreground class k is refined from its own columns 4(k+1)..4(k+1)+3
+        (learn_nms.py:283-287); after the per-class sort sorted_bbox[r,k] is class k's box of roi idx[r,k] (:311-321)."""
         t = lambda x, dt: torch.as_tensor(x).to(device=device, dtype=dt).contiguous()
         p = params
-        self.dtype, self.device = dtype, device
+        self.dtype, self.device, self.class_agnostic = dtype, device, bool(class_agnostic)
         self.C, self.F, self.T = num_fg_classes, first_n, num_thresh
         self.class_thresh, self.merge, self.score_thresh, self.max_per_image = class_thresh, merge_method, score_thresh, max_per_image
         self.means = None if bbox_means is None else (ctypes.c_float * 4)(*[float(v) for v in bbox_means])
@@ -71,16 +73,23 @@ class LearnNMS(object):
         bp = bbox_pred.reshape(B * N, -1)
         assert cs.stride(1) == 1 and bp.stride(1) == 1 and cs.dtype == torch.float32 and bp.dtype == torch.float32
         prob = torch.empty((B, N, C), device=dev, dtype=torch.float32)
-        boxes = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
-        _lib.call('relnet_lnms_prepare_ex', cs.data_ptr(), cs.stride(0), bp.data_ptr(), bp.stride(0), rois.data_ptr(),
-                  im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, 4, self.means, self.stds,
-                  ops._ptr(n_valid), s)       # n_valid [B] int32: rows past it are padding (probability 0: they sort last)
+        if self.class_agnostic:
+            boxes = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
+            _lib.call('relnet_lnms_prepare_ex', cs.data_ptr(), cs.stride(0), bp.data_ptr(), bp.stride(0), rois.data_ptr(),
+                      im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, 4, self.means, self.stds,
+                      ops._ptr(n_valid), s)       # n_valid [B] int32: rows past it are padding (probability 0: they sort last)
+        else:
+            if bp.shape[1] != 4 * C1:
+                raise ValueError("class-specific bbox_pred must have 4 * %d columns, got %d" % (C1, bp.shape[1]))
+            boxes = torch.empty((B, N, C, 4), device=dev, dtype=torch.float32)
+            _lib.call('relnet_lnms_prepare_cs', cs.data_ptr(), cs.stride(0), bp.data_ptr(), bp.stride(0), rois.data_ptr(),
+                      im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, self.means, self.stds, ops._ptr(n_valid), s)
         rank_idx = torch.empty((B, C, F), device=dev, dtype=torch.int32)
         sorted_score = torch.empty((B, F, C), device=dev, dtype=torch.float32)
         sorted_bbox = torch.empty((B, F, C, 4), device=dev, dtype=torch.float32)
         class_boxes = torch.empty((B, C, F, 4), device=dev, dtype=torch.float32)
         class_max = torch.empty((B, C), device=dev, dtype=torch.float32)
-        _lib.call('relnet_lnms_sort', prob.data_ptr(), boxes.data_ptr(), rank_idx.data_ptr(), sorted_score.data_ptr(),
+        _lib.call('relnet_lnms_sort' if self.class_agnostic else 'relnet_lnms_sort_cs', prob.data_ptr(), boxes.data_ptr(), rank_idx.data_ptr(), sorted_score.data_ptr(),
                   sorted_bbox.data_ptr(), class_boxes.data_ptr(), class_max.data_ptr(), B, N, C, F, s)
         # (feat may carry rows past N -- the gt rows of a training graph: learn_nms.py:335-339 embeds fc_all_2_relu unsliced and
         #  takes rows by rank, so the ranks only ever address its first N rows)

@@ -62,6 +62,12 @@ _SIGNATURES = {
     'relnet_class_nms_ex': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.c_double, _i, _i, _vp]),
     'relnet_class_nms_topk': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.c_double, _i, _i, _i, _vp]),
     'relnet_class_nms_hist_bins': (C.c_int, []),
+    # class-specific box regression (CLASS_AGNOSTIC false): boxes [R,C,4] / [B,N,C,4]
+    'relnet_detect_head_cs': (C.c_int, [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'relnet_class_nms_cs': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.c_double, _i, _i, _vp]),
+    'relnet_class_nms_topk_cs': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.c_double, _i, _i, _i, _vp]),
+    'relnet_lnms_prepare_cs': (C.c_int, [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'relnet_lnms_sort_cs': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'relnet_bbox_overlaps': (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
     'relnet_image_topk': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'relnet_conv2d_nhwc': (C.c_int, [_vp, _l, _l, _vp, _vp, _vp, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

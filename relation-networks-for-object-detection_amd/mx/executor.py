@@ -77,8 +77,19 @@ def _t(x, device):
     return x.to(device)
 
 
+def check_class_agnostic(sym):
+    """The facade runs the class-agnostic graphs only (num_reg_classes = 2: `bbox_pred` is a FullyConnected of 8 outputs).  A graph built
+    with CLASS_AGNOSTIC false has 4 * num_classes of them and a learn_nms node that reads them per class: refused at bind time rather than
+    run with class 1's box for every class.  (detector.Detector / train.Trainer with cfg.class_agnostic = False run that model.)"""
+    for node in sym._topo():
+        if node.op == 'FullyConnected' and node.name == 'bbox_pred' and R.a_int(node.attrs, 'num_hidden') != 8:
+            raise NotImplementedError("bbox_pred has num_hidden=%d: class-specific box regression (CLASS_AGNOSTIC false) is not "
+                                      "supported by the mx facade" % R.a_int(node.attrs, 'num_hidden'))
+
+
 class Executor(object):
     def __init__(self, sym, args, aux_states, ctx=None, dtype=torch.bfloat16, fuse=True, probe=True, device='cuda'):
+        check_class_agnostic(sym)
         if not torch.cuda.is_available():
             raise _lib.RelnetError("the mx executor runs on the GPU only (HIP kernels; no CPU fallback)")
         _lib.load()

@@ -17,7 +17,7 @@ class LearnNmsOperator(CustomOp):
     def __init__(self, num_fg_classes, bbox_means, bbox_stds, first_n, class_agnostic, num_thresh, class_thresh,
                  nongt_dim=None, has_non_gt_index=False):
         super(LearnNmsOperator, self).__init__()
-        assert class_agnostic, "class-specific regression is not used by any shipped cfg"
+        self.class_agnostic = bool(class_agnostic)
         self.num_fg_classes, self.first_n, self.num_thresh = num_fg_classes, first_n, num_thresh
         self.bbox_means, self.bbox_stds, self.class_thresh, self.nongt_dim = bbox_means, bbox_stds, class_thresh, nongt_dim
         self.has_non_gt_index = has_non_gt_index
@@ -38,7 +38,7 @@ class LearnNmsOperator(CustomOp):
             params = dict(zip(ARGS[5:], in_data[5:19]))
             self._impl = LearnNMS(params, self.num_fg_classes, self.first_n, self.num_thresh, self.class_thresh,
                                   self.bbox_means, self.bbox_stds, dtype=feat.dtype if feat.dtype != torch.float64 else torch.float32,
-                                  device=cls_score.device)
+                                  device=cls_score.device, class_agnostic=self.class_agnostic)
             self._key = key
         r = self._impl.forward(cls_score[None].float().contiguous(), bbox_pred[None].float().contiguous(), rois[None].float().contiguous(),
                                im_info.reshape(-1, 3).float().contiguous(), feat[None].contiguous(), want_detections=False)

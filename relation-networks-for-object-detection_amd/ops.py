@@ -417,15 +417,25 @@ def roi_align_bwd(grad_out, rois, in_shape, spatial_scale=0.0625, sampling_ratio
 # ---------------------------------------------------------------------------------------
 # detection post-processing
 # ---------------------------------------------------------------------------------------
-def detect_head(cls_score, bbox_pred, rois, im_info, rois_per_image, delta_off=4, n_valid=None):
+def detect_head(cls_score, bbox_pred, rois, im_info, rois_per_image, delta_off=4, n_valid=None, class_agnostic=True):
     """cls_score [R,C] fp32 logits, bbox_pred [R,4*num_reg] fp32, rois [R,5], im_info [B,3]
     -> cls_prob [R,C] fp32, boxes [R,4] float64 (decoded class-agnostic fg box / im scale).
-    n_valid [B] int32 (optional): rows past n_valid[b] of image b are padding -> all-zero probabilities and boxes."""
+    n_valid [B] int32 (optional): rows past n_valid[b] of image b are padding -> all-zero probabilities and boxes.
+    class_agnostic=False (CLASS_AGNOSTIC false, tester.py:148-156,253): bbox_pred is [R,4*C], every class is decoded from its own
+    four columns -> boxes [R,C,4] (background included; delta_off has no meaning)."""
     _chk(cls_score, bbox_pred, rois, im_info, n_valid)
     R, Cn = cls_score.shape
     assert cls_score.dtype == torch.float32 and bbox_pred.dtype == torch.float32
     assert cls_score.stride(1) == 1 and bbox_pred.stride(1) == 1 and rois.is_contiguous()
     prob = torch.empty((R, Cn), device=cls_score.device, dtype=torch.float32)
+    if not class_agnostic:
+        if bbox_pred.shape[1] != 4 * Cn:
+            raise ValueError("class-specific bbox_pred must have 4 * %d columns, got %d" % (Cn, bbox_pred.shape[1]))
+        boxes = torch.empty((R, Cn, 4), device=cls_score.device, dtype=torch.float64)
+        _lib.call('relnet_detect_head_cs', cls_score.data_ptr(), cls_score.stride(0), bbox_pred.data_ptr(), bbox_pred.stride(0),
+                  rois.data_ptr(), im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), R, Cn, rois_per_image, _ptr(n_valid),
+                  _stream())
+        return prob, boxes
     boxes = torch.empty((R, 4), device=cls_score.device, dtype=torch.float64)
     _lib.call('relnet_detect_head_ex', cls_score.data_ptr(), cls_score.stride(0), bbox_pred.data_ptr(),
               bbox_pred.stride(0), rois.data_ptr(), im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(),
@@ -435,8 +445,8 @@ def detect_head(cls_score, bbox_pred, rois, im_info, rois_per_image, delta_off=4
 
 def class_nms(cls_prob, boxes, score_thresh=1e-3, nms_param=0.6, soft=True, max_picks=0, scores64=None,
               want_index=False, top_k=0):
-    """cls_prob [B,N,C] fp32, boxes [B,N,4] float64 -> dets [B,C-1,N,5] float64 (pick order),
-    counts [B,C-1] int32.  max_picks > 0 truncates every class list after that many picks
+    """cls_prob [B,N,C] fp32, boxes [B,N,4] float64 (one box per roi for every class) or [B,N,C,4] (class-specific: class j's list
+    uses boxes[:, :, j], tester.py:253) -> dets [B,C-1,N,5] float64 (pick order), counts [B,C-1] int32.  max_picks > 0 truncates every class list after that many picks
     (exactly the rows that can survive the image-level max_per_image cut).
     scores64 [B,N] float64 (one class; cls_prob None) is the `dets[:, 4]` form of lib/nms/nms.py;
     want_index also returns pick_index [B,C-1,N] int32 (roi index of every pick).
@@ -450,15 +460,21 @@ def class_nms(cls_prob, boxes, score_thresh=1e-3, nms_param=0.6, soft=True, max_
     else:
         B, N, Cn = cls_prob.shape
         assert cls_prob.is_contiguous() and cls_prob.dtype == torch.float32
-    assert boxes.is_contiguous() and boxes.dtype == torch.float64 and boxes.shape == (B, N, 4)
+    cs = boxes.dim() == 4
+    assert boxes.is_contiguous() and boxes.dtype == torch.float64 and boxes.shape == ((B, N, Cn, 4) if cs else (B, N, 4))
+    assert not (cs and scores64 is not None), "float64 scores are the single-class form: pass that class's boxes [B,N,4]"
     dets = torch.zeros((B, Cn - 1, N, 5), device=boxes.device, dtype=torch.float64)
     counts = torch.empty((B, Cn - 1), device=boxes.device, dtype=torch.int32)
     index = torch.full((B, Cn - 1, N), -1, device=boxes.device, dtype=torch.int32) if want_index else None
     if top_k > 0 and scores64 is None and not want_index and N <= 1024:
         hist = torch.zeros((B, _lib.load().relnet_class_nms_hist_bins()), device=boxes.device, dtype=torch.int32)
-        _lib.call('relnet_class_nms_topk', cls_prob.data_ptr(), boxes.data_ptr(), dets.data_ptr(), counts.data_ptr(), hist.data_ptr(),
+        _lib.call('relnet_class_nms_topk_cs' if cs else 'relnet_class_nms_topk', cls_prob.data_ptr(), boxes.data_ptr(), dets.data_ptr(), counts.data_ptr(), hist.data_ptr(),
                   B, N, Cn, float(score_thresh), float(nms_param), int(soft), int(max_picks), int(top_k), _stream())
         return dets, counts
+    if cs:
+        _lib.call('relnet_class_nms_cs', cls_prob.data_ptr(), boxes.data_ptr(), dets.data_ptr(), counts.data_ptr(), _ptr(index),
+                  B, N, Cn, float(score_thresh), float(nms_param), int(soft), int(max_picks), _stream())
+        return (dets, counts, index) if want_index else (dets, counts)
     _lib.call('relnet_class_nms_ex', _ptr(cls_prob), _ptr(scores64), boxes.data_ptr(), dets.data_ptr(), counts.data_ptr(),
               _ptr(index), B, N, Cn, float(score_thresh), float(nms_param), int(soft), int(max_picks), _stream())
     return (dets, counts, index) if want_index else (dets, counts)

@@ -77,8 +77,27 @@ def all_reduce_sum(*buffers):
             torch.cuda.synchronize()            # gloo on device tensors (one-GPU test path), see dist.BucketedAllReduce.finish
 
 
+def box_target_layout(cfg):
+    """The regression-target layout the trainers ask ops.proposal_target for (lib/bbox/bbox_regression.py:129-140): [R, 8] with the target
+    at columns 4..7 when class agnostic, else [R, 4 * num_classes] with the four entries at 4 * label."""
+    agnostic = bool(getattr(cfg, 'class_agnostic', True))
+    return dict(num_reg=2 if agnostic else cfg.num_classes, class_agnostic=agnostic)
+
+
+def check_box_head(cfg, params):
+    """cfg.class_agnostic, cfg.num_classes and the parameters' cls_score / bbox_pred rows must describe one head (symbols/...:157
+    num_reg_classes = 2 if CLASS_AGNOSTIC else num_classes)."""
+    rows, nc = int(params['bbox_pred_weight'].shape[0]), int(params['cls_score_weight'].shape[0])
+    agnostic = bool(getattr(cfg, 'class_agnostic', True))
+    want = 8 if agnostic else 4 * nc
+    if rows != want or (not agnostic and nc != cfg.num_classes):
+        raise ValueError("class_agnostic=%s with %d classes (cfg.num_classes %d) needs a bbox_pred_weight of %d rows, got %d"
+                         % (agnostic, nc, cfg.num_classes, want, rows))
+
+
 def check_deterministic(cfg):
-    """cfg.deterministic covers the C4 graphs with ROIPooling.  The other pooling operators and the deformable convolutions still accumulate
+    """cfg.deterministic covers the C4 graphs with ROIPooling, class-agnostic or class-specific (cfg.class_agnostic = False adds no float
+    accumulation: wider targets, the per-class geometry branch of the learn-NMS head).  The other pooling operators and the deformable convolutions still accumulate
     with float atomics, whose order the hardware decides: refused by name rather than silently not reproducible."""
     if not getattr(cfg, 'deterministic', False):
         return
@@ -183,8 +202,10 @@ class Trainer(object):
         self.cfg = cfg or TrainConfig()
         check_pooling(self.cfg)
         check_deterministic(self.cfg)
+        check_box_head(self.cfg, params)
         self.device, self.im_hw = device, im_hw
         c = self.cfg
+        self.class_agnostic = bool(getattr(c, 'class_agnostic', True))
         self.deterministic = bool(getattr(c, 'deterministic', False))       # read ONCE: every site below routes on this attribute
         dev = device
         f32 = lambda t: torch.as_tensor(t).to(dev, torch.float32).contiguous()
@@ -542,7 +563,7 @@ class Trainer(object):
                                     c.rpn_pre_nms_top_n, c.rpn_post_nms_top_n, c.rpn_nms_thresh, c.rpn_min_size,
                                     im_hw=self.im_hw, softmax_pairs=True)
             N = rois.shape[1]
-            rois_t, label, bbox_target, bbox_weight = ops.proposal_target(rois, gt_boxes, num_gt)
+            rois_t, label, bbox_target, bbox_weight = ops.proposal_target(rois, gt_boxes, num_gt, **box_target_layout(c))
             R = rois_t.shape[1]
             br.update(r=r, d_rpn=d_rpn, rois_t=rois_t, label=label, bbox_target=bbox_target, bbox_weight=bbox_weight, N=N, R=R)
             if rpn_bwd_side:
@@ -812,7 +833,7 @@ class Trainer(object):
 
     def _lnms_forward_backward(self, cls_score, bbox_pred, rois, im_info, feat, gt_boxes, num_gt, n_valid=None, d_cls_out=None):
         """Train branch of the learn-NMS head (symbols/..._learn_nms.py:424-551) and its adjoint.
-        cls_score [B,N,81] fp32, bbox_pred [B,N,8] (BlockGrad), rois [B,N,5], feat = fc_all_2_relu[:, :N] bf16.
+        cls_score [B,N,81] fp32, bbox_pred [B,N,8] ([B,N,4*81] class-specific: learn_nms.py:283-287,311-321) (BlockGrad), rois [B,N,5], feat = fc_all_2_relu[:, :N] bf16.
         Returns (d cls_score [B,N,81] fp32, d feat [B,N,1024] (bf16, as the projection's backward GEMM leaves it), losses); with d_cls_out [B,R,81] fp32 (contiguous, R >= N) the
         class-score gradient is accumulated into d_cls_out[:, :N] instead and None is returned in its place.
         cfg.lnms_fused_glue (default on; off = the tensor-operator chains of rounds 3 - 5, kept for the equality test):
@@ -826,17 +847,23 @@ class Trainer(object):
         dev, bt, s_ = cls_score.device, torch.bfloat16, ops._stream()
         cs, bp_ = cls_score.contiguous().view(B * N, C1), bbox_pred.contiguous().view(B * N, -1)
         prob = torch.empty((B, N, C), device=dev, dtype=torch.float32)
-        boxes = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
         means, stds = (ctypes.c_float * 4)(*c.bbox_means), (ctypes.c_float * 4)(*c.bbox_stds)
-        _lib.call('relnet_lnms_prepare_ex', cs.data_ptr(), cs.stride(0), bp_.data_ptr(), bp_.stride(0), rois.data_ptr(),
-                  im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, 4, means, stds, ops._ptr(n_valid), s_)
+        if self.class_agnostic:
+            boxes = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
+            _lib.call('relnet_lnms_prepare_ex', cs.data_ptr(), cs.stride(0), bp_.data_ptr(), bp_.stride(0), rois.data_ptr(),
+                      im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, 4, means, stds, ops._ptr(n_valid), s_)
+        else:       # every foreground class refined from its own four columns
+            assert bp_.shape[1] == 4 * C1, bp_.shape
+            boxes = torch.empty((B, N, C, 4), device=dev, dtype=torch.float32)
+            _lib.call('relnet_lnms_prepare_cs', cs.data_ptr(), cs.stride(0), bp_.data_ptr(), bp_.stride(0), rois.data_ptr(),
+                      im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, means, stds, ops._ptr(n_valid), s_)
         rank_idx = torch.empty((B, C, F), device=dev, dtype=torch.int32)
         sorted_score = torch.empty((B, F, C), device=dev, dtype=torch.float32)
         sorted_bbox = torch.empty((B, F, C, 4), device=dev, dtype=torch.float32)
         class_boxes = torch.empty((B, C, F, 4), device=dev, dtype=torch.float32)
         class_max = torch.empty((B, C), device=dev, dtype=torch.float32)
-        _lib.call('relnet_lnms_sort', prob.data_ptr(), boxes.data_ptr(), rank_idx.data_ptr(), sorted_score.data_ptr(),
-                  sorted_bbox.data_ptr(), class_boxes.data_ptr(), class_max.data_ptr(), B, N, C, F, s_)
+        _lib.call('relnet_lnms_sort' if self.class_agnostic else 'relnet_lnms_sort_cs', prob.data_ptr(), boxes.data_ptr(), rank_idx.data_ptr(),
+                  sorted_score.data_ptr(), sorted_bbox.data_ptr(), class_boxes.data_ptr(), class_max.data_ptr(), B, N, C, F, s_)
         rank_feat = ops.gemm_nt(self.rank_emb, self.w('nms_rank'), self.b('nms_rank'), out_dtype=torch.float32)      # [F,128]
         feat2 = feat.contiguous().view(B * N, -1)
         roi_emb = ops.gemm_nt(feat2, self.w('roi_feat_embedding'), self.b('roi_feat_embedding'))
@@ -864,13 +891,14 @@ class Trainer(object):
         mod.bp = self.b('nms_pair_pos_fc1_1')
         wp_t, bp = pack_pair_pos([mod], dev)
         cb = class_boxes.view(BC, F, 4)
-        if fused and n_valid is None:
+        if fused and n_valid is None and self.class_agnostic:
             # ln G once per IMAGE (B N^2 pairs instead of B C F^2: 9 x fewer at 300 rois / 80 classes / first_n 100), then gathered per class by its ranks
             # (relnet_lnms_gather_bias): the class's boxes are the image's boxes re-ordered, same arithmetic on the same pairs -> bit-identical
+            assert boxes.shape == (B, N, 4), "the per-image shortcut needs ONE box per roi (class-agnostic regression)"
             img = ops.geometry_bias(boxes, wp_t, bp, N, fast32=True)[0]                    # [B,16,N,Npad]
             bias = torch.empty((BC, 16, F, ops.pad32(F)), device=dev, dtype=torch.float32)
             _lib.call('relnet_lnms_gather_bias', img.data_ptr(), rank_idx.data_ptr(), bias.data_ptr(), B, C, N, img.shape[-1], F, bias.shape[-1], s_)
-        else:
+        else:       # (class-specific boxes: a class's boxes are NOT the image's boxes re-ordered, every class has its own N -- the shortcut's premise is false)
             bias = ops.geometry_bias(cb, wp_t, bp, F, fast32=True)[0]
         lcache = {}
         att, _, _ = _module_forward(xr, mod, bias, F, True, False, False, vwt_buf=self._scratch('vwt_nms_%d' % F, (BC, 1024, bias.shape[-1]), bt),
@@ -1401,7 +1429,7 @@ class FPNTrainer(Trainer):
         # ---- rois: labels / targets, then level dispatch (non-gt rows first, gt rows after)
         rois5 = torch.cat([torch.zeros((B, N, 1), device=proposals.device), proposals], 2)
         rois5[:, :, 0] = torch.arange(B, device=proposals.device, dtype=torch.float32).view(B, 1)
-        rois_t, label, bbox_target, bbox_weight = ops.proposal_target(rois5.contiguous(), gt_boxes, num_gt, num_rois=num_proposals)
+        rois_t, label, bbox_target, bbox_weight = ops.proposal_target(rois5.contiguous(), gt_boxes, num_gt, num_rois=num_proposals, **box_target_layout(self.cfg))
         R = rois_t.shape[1]
         key_count = None
         if num_proposals is not None:
