@@ -385,6 +385,36 @@ int relnet_proposal_target_ex(const float* rois, const float* gt, const int* num
                               float* bbox_target, float* bbox_weight, int B, int N, int Gmax, int num_reg,
                               int class_agnostic, float bg_thresh_hi, const double* means4, const double* stds4,
                               const double* weights4, const int* num_rois, void* stream);
+/* Sampled ROI minibatch: operator_py/proposal_target.py:50-78 with BATCH_ROIS > 0 (append_gt 1) or < -10 (append_gt 0) ->
+ * core/rcnn.py:329-397 (sample_rois).  rois [B,N,5], gt [B,Gmax,5], num_gt [B], num_rois [B] (may be NULL: N); outputs
+ * rois_out [B,R,5], label [B,R], bbox_target / bbox_weight [B,R,4*num_reg], keep_index [B,R] int32 (the candidate each
+ * row was taken from), R = rois_per_image.  Per image b:
+ *   candidates  i in [0, M): the first num_rois[b] proposals, then (append_gt) the num_gt[b] gt rows (:64-67)
+ *   overlap     ov[i] = float64 maximum IoU over the valid gt boxes, matched gt = first maximum (the arithmetic of
+ *               relnet_proposal_target_ex); thresholds are compared as float64, like the reference's Python floats
+ *   sets        fg = {ov >= fg_thresh}, bg = {bg_thresh_lo <= ov < bg_thresh_hi}
+ *   counts      fg_take = min(fg_rois_per_image, |fg|), bg_take = min(R - fg_take, |bg|)   (rcnn.py:350-364)
+ *   subset      a set larger than its take is cut to the take members with the smallest 64-bit word
+ *               (key32(seed + *seed_dev, b, stream, i) << 32) | i; key32 = the avalanche hash of relnet_assign_anchor with
+ *               stream * 0x27D4EB2F xor-ed into its input (stream 0 fg, 1 bg, 2 + t padding round t); a set not larger
+ *               than its take is used whole
+ *   order       chosen fg in ascending i, then chosen bg in ascending i (the reference's order whenever it makes no
+ *               npr.choice call)
+ *   padding     while fewer than R rows: gap = min(M, R - have); the gap candidates of ALL M with the smallest words of
+ *               stream 2 + t, in ascending i, are appended (:370-373) -- they may repeat kept rows and may be in neither set
+ *   rows        label = the matched gt's class, 0 where ov < bg_thresh_hi (:378-381); targets / weights as
+ *               relnet_proposal_target_ex makes them for the same (roi, matched gt); the image-index column of a gt row is b
+ *   outside the reference's domain: M = 0 -> zero boxes, label -1, zero weights, keep_index -1 (the reference would loop);
+ *               num_gt[b] = 0 -> every overlap is 0 (the reference raises)
+ * One workgroup per image, integer LDS atomics only, no host synchronisation; seed_dev (may be NULL) as in
+ * relnet_assign_anchor, so a captured graph draws a new sample on every replay.  Limit: N + (append_gt ? Gmax : 0) <= 8192
+ * candidates per image (their words live in 64 KB of LDS); larger inputs are refused.                                  */
+int relnet_proposal_target_sample(const float* rois, const float* gt, const int* num_gt, const int* num_rois,
+                                  float* rois_out, float* label, float* bbox_target, float* bbox_weight, int* keep_index,
+                                  int B, int N, int Gmax, int rois_per_image, int fg_rois_per_image, double fg_thresh,
+                                  double bg_thresh_hi, double bg_thresh_lo, int append_gt, int num_reg, int class_agnostic,
+                                  const double* means4, const double* stds4, const double* weights4,
+                                  unsigned long long seed, const unsigned long long* seed_dev, void* stream);
 /* lib/rpn/rpn.py:80-244 `assign_anchor(feat_shape, gt_boxes, im_info, cfg, feat_stride, scales, ratios, allowed_border)`
  * -- RPN labels / regression targets, host numpy inside the reference's data loader -- for B images on the device.
  * gt [B,Gmax,5] float32, num_gt [B], im_info [B,3]; base_anchors: HOST double [A,4] (generate_anchors); outputs in the

@@ -18,6 +18,49 @@ __device__ __forceinline__ double iou64(const double* a, const double* b) {
   return iw * ih / ua;
 }
 
+// One (roi, gt list) pair of sample_rois_v2 / sample_rois, shared by the all-rows and the sampled kernel: pt_max_overlap = the float64
+// maximum overlap and its first argmax; pt_label_targets = the label (0 below bg_thresh_hi) and the regression target / weight columns of
+// the matched gt written into the (zeroed) rows bt / bwp.
+__device__ __forceinline__ double pt_max_overlap(const float* box, const float* gtb, int G, int* bi_out) {
+  const double a[4] = {box[0], box[1], box[2], box[3]};
+  double best = -1.0; int bi = 0;
+  for (int k = 0; k < G; ++k) {
+    const double q[4] = {gtb[k * 5], gtb[k * 5 + 1], gtb[k * 5 + 2], gtb[k * 5 + 3]};
+    const double ov = iou64(a, q);
+    if (ov > best) { best = ov; bi = k; }   // argmax: first maximum
+  }
+  *bi_out = bi;
+  return best;
+}
+
+__device__ __forceinline__ float pt_label_targets(const float* box, const float* gtb, int G, double bg_thresh_hi, int num_reg,
+                                                  int class_agnostic, const double* mean, const double* stdv, const double* bw,
+                                                  float* bt, float* bwp) {
+  float lab = 0.f;
+  if (G > 0) {
+    int bi;
+    const double best = pt_max_overlap(box, gtb, G, &bi);
+    lab = gtb[bi * 5 + 4];
+    if (best < bg_thresh_hi) lab = 0.f;                                 // rcnn.py:309-310
+    if (lab > 0.f && (class_agnostic || (int)lab < num_reg)) {          // (class-specific: a label past num_reg has no columns to write)
+      // bbox_transform.py:74-100 on float32 arrays (numpy keeps float32), log correctly rounded
+      const float* q = gtb + bi * 5;
+      const float ew = box[2] - box[0] + 1.0f, eh = box[3] - box[1] + 1.0f;
+      const float ecx = box[0] + 0.5f * (ew - 1.0f), ecy = box[1] + 0.5f * (eh - 1.0f);
+      const float gw = q[2] - q[0] + 1.0f, gh = q[3] - q[1] + 1.0f;
+      const float gcx = q[0] + 0.5f * (gw - 1.0f), gcy = q[1] + 0.5f * (gh - 1.0f);
+      const float t[4] = {(gcx - ecx) / (ew + 1e-14f), (gcy - ecy) / (eh + 1e-14f),
+                          (float)log((double)(gw / ew)), (float)log((double)(gh / eh))};
+      const int start = class_agnostic ? 4 : 4 * (int)lab;              // bbox_regression.py:134-138
+      for (int c = 0; c < 4; ++c) {
+        bt[start + c] = (float)(((double)t[c] - mean[c]) / stdv[c]);
+        bwp[start + c] = (float)bw[c];
+      }
+    }
+  }
+  return lab;
+}
+
 struct PTArgs {
   const float* rois;      // [B, N, 5]
   const float* gt;        // [B, Gmax, 5]  x1,y1,x2,y2,cls
@@ -58,34 +101,7 @@ __global__ __launch_bounds__(256) void proposal_target_kernel(PTArgs g) {
     for (int c = 0; c < 4; ++c) box[c] = gtb[(r - g.N) * 5 + c];
   }
   for (int c = 0; c < 4; ++c) ro[1 + c] = box[c];
-  float lab = 0.f;
-  if (G > 0) {
-    const double a[4] = {box[0], box[1], box[2], box[3]};
-    double best = -1.0; int bi = 0;
-    for (int k = 0; k < G; ++k) {
-      const double q[4] = {gtb[k * 5], gtb[k * 5 + 1], gtb[k * 5 + 2], gtb[k * 5 + 3]};
-      const double ov = iou64(a, q);
-      if (ov > best) { best = ov; bi = k; }   // argmax: first maximum
-    }
-    lab = gtb[bi * 5 + 4];
-    if (best < (double)g.bg_thresh_hi) lab = 0.f;                      // rcnn.py:309-310
-    if (lab > 0.f && (g.class_agnostic || (int)lab < g.num_reg)) {      // (class-specific: a label past num_reg has no columns to write)
-      // bbox_transform.py:74-100 on float32 arrays (numpy keeps float32), log correctly rounded
-      const float* q = gtb + bi * 5;
-      const float ew = box[2] - box[0] + 1.0f, eh = box[3] - box[1] + 1.0f;
-      const float ecx = box[0] + 0.5f * (ew - 1.0f), ecy = box[1] + 0.5f * (eh - 1.0f);
-      const float gw = q[2] - q[0] + 1.0f, gh = q[3] - q[1] + 1.0f;
-      const float gcx = q[0] + 0.5f * (gw - 1.0f), gcy = q[1] + 0.5f * (gh - 1.0f);
-      const float t[4] = {(gcx - ecx) / (ew + 1e-14f), (gcy - ecy) / (eh + 1e-14f),
-                          (float)log((double)(gw / ew)), (float)log((double)(gh / eh))};
-      const int start = g.class_agnostic ? 4 : 4 * (int)lab;          // bbox_regression.py:134-138
-      for (int c = 0; c < 4; ++c) {
-        bt[start + c] = (float)(((double)t[c] - g.mean[c]) / g.stdv[c]);
-        bwp[start + c] = (float)g.bw[c];
-      }
-    }
-  }
-  g.label[(long)b * R + r] = lab;
+  g.label[(long)b * R + r] = pt_label_targets(box, gtb, G, (double)g.bg_thresh_hi, g.num_reg, g.class_agnostic, g.mean, g.stdv, g.bw, bt, bwp);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -434,6 +450,180 @@ __global__ __launch_bounds__(1024) void anchor_sample_kernel(AnchorArgs g) {
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Sampled ROI minibatch (reference: operator_py/proposal_target.py:50-78 with BATCH_ROIS > 0 or < -10 -> core/rcnn.py:329-397
+// sample_rois): R rows per image, at most fg_rois of them foreground, chosen at random, padded to R (include/relnet_hip.h states the
+// rule).  One workgroup per image: overlaps -> fg / bg flags in LDS; per random draw (fg, bg, each padding round) the 64-bit
+// (key, index) words of the set live in LDS, the `take` smallest are found by the 8-bit radix select of anchor_sample_kernel, and a
+// prefix scan over the chosen flags writes them in ascending candidate order; then one thread per output row makes the label and the
+// targets with the all-rows kernel's arithmetic.  Integer LDS atomics only, no host synchronisation.
+// ---------------------------------------------------------------------------------------
+constexpr int kPtsMax = 8192;       // candidates per image (N + Gmax): 8192 words of 8 bytes = 64 KB of LDS
+constexpr int kPtsThreads = 1024;
+
+struct PTSArgs {
+  const float* rois;      // [B, N, 5]
+  const float* gt;        // [B, Gmax, 5]
+  const int* num_gt;      // [B]
+  const int* num_rois;    // optional [B]
+  float* rois_out;        // [B, R, 5]
+  float* label;           // [B, R]
+  float* bbox_target;     // [B, R, 4*num_reg]
+  float* bbox_weight;     // [B, R, 4*num_reg]
+  int* keep_index;        // [B, R]
+  int N, Gmax, R, fg_rois, append_gt, num_reg, class_agnostic;
+  double fg_thresh, bg_thresh_hi, bg_thresh_lo;
+  double mean[4], stdv[4], bw[4];
+  unsigned long long seed;
+  const unsigned long long* seed_dev;
+};
+
+__device__ __forceinline__ unsigned int roi_key(unsigned long long seed, int b, int stream, int idx) {
+  // anchor_key with a stream number mixed in (stream 0 = anchor_key itself): 0 fg, 1 bg, 2 + t padding round t
+  unsigned int x = (unsigned int)idx * 0x9E3779B1u ^ (unsigned int)(seed & 0xffffffffu) ^ ((unsigned int)b * 0x85EBCA77u)
+                   ^ (unsigned int)(seed >> 32) * 0xC2B2AE3Du ^ (unsigned int)stream * 0x27D4EB2Fu;
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+
+__global__ __launch_bounds__(kPtsThreads) void proposal_target_sample_kernel(PTSArgs g) {
+  __shared__ unsigned long long s_word[kPtsMax];     // words of the current draw (all ones: not in the set)
+  __shared__ unsigned char s_set[kPtsMax];           // bit 0: fg, bit 1: bg
+  __shared__ int s_hist[256];
+  __shared__ int s_red[kPtsThreads / 64];
+  __shared__ int s_pick[2];                          // chosen digit, remaining rank
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int R = g.R, D = 4 * g.num_reg;
+  const int G = min(max(g.num_gt[b], 0), g.Gmax);
+  const int nr = g.num_rois ? min(max(g.num_rois[b], 0), g.N) : g.N;
+  const int M = nr + (g.append_gt ? G : 0);          // candidates: the proposals, then the gt rows (proposal_target.py:64-67)
+  const float* gtb = g.gt + (long)b * g.Gmax * 5;
+  int* keep = g.keep_index + (long)b * R;
+  if (M == 0) {                                      // (the reference would pad forever)
+    for (int r = tid; r < R; r += kPtsThreads) {
+      float* ro = g.rois_out + ((long)b * R + r) * 5;
+      for (int c = 0; c < 5; ++c) ro[c] = 0.f;
+      ro[0] = (float)b;                              // still a valid image index for the batched pooling kernels
+      for (int c = 0; c < D; ++c) { g.bbox_target[((long)b * R + r) * D + c] = 0.f; g.bbox_weight[((long)b * R + r) * D + c] = 0.f; }
+      g.label[(long)b * R + r] = -1.f;
+      keep[r] = -1;
+    }
+    return;
+  }
+  const unsigned long long seed = g.seed + (g.seed_dev ? *g.seed_dev : 0ull);
+  auto cand_box = [&](int i, float* box) -> float {  // candidate i: box and the image index column
+    if (i < nr) {
+      const float* p = g.rois + ((long)b * g.N + i) * 5;
+      for (int c = 0; c < 4; ++c) box[c] = p[1 + c];
+      return p[0];
+    }
+    for (int c = 0; c < 4; ++c) box[c] = gtb[(i - nr) * 5 + c];
+    return (float)b;
+  };
+  auto block_sum = [&](int c) -> int {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    __syncthreads();
+    if (lane == 0) s_red[wave] = c;
+    __syncthreads();
+    int t = 0;
+    for (int w = 0; w < kPtsThreads / 64; ++w) t += s_red[w];
+    return t;
+  };
+  // ---- overlaps -> sets (rcnn.py:344-346, 350, 358)
+  int cfg = 0, cbg = 0;
+  for (int i = tid; i < M; i += kPtsThreads) {
+    float box[4];
+    cand_box(i, box);
+    double ov = 0.0;                                 // no gt boxes: every overlap is 0
+    if (G > 0) { int bi; ov = pt_max_overlap(box, gtb, G, &bi); }
+    const int fg = ov >= g.fg_thresh ? 1 : 0, bg = (ov < g.bg_thresh_hi && ov >= g.bg_thresh_lo) ? 1 : 0;
+    s_set[i] = (unsigned char)(fg | (bg << 1));
+    cfg += fg; cbg += bg;
+  }
+  const int nfg = block_sum(cfg), nbg = block_sum(cbg);
+  const int fg_take = min(min(g.fg_rois, nfg), R);   // rcnn.py:352
+  const int bg_take = min(R - fg_take, nbg);         // rcnn.py:360-361
+  // One draw: the `take` members of a set of n (mask 0: all candidates) with the smallest words of `stream`, written to
+  // keep[base ...] in ascending candidate order.  Every argument is a block-wide value.
+  auto select_emit = [&](int stream, int mask, int n, int take, int base) {
+    if (take <= 0) return;
+    const bool cut = n > take;                       // a set not larger than its take is used whole
+    unsigned long long thr = ~0ull;
+    if (cut) {
+      for (int i = tid; i < M; i += kPtsThreads)
+        s_word[i] = (mask == 0 || (s_set[i] & mask)) ? (((unsigned long long)roi_key(seed, b, stream, i) << 32) | (unsigned int)i) : ~0ull;
+      unsigned long long prefix = 0ull, pmask = 0ull;
+      int need = take;                               // rank (1-based) of the threshold word among the words matching `prefix`
+      for (int shift = 56; shift >= 0; shift -= 8) {
+        if (tid < 256) s_hist[tid] = 0;
+        __syncthreads();
+        for (int i = tid; i < M; i += kPtsThreads) {
+          const unsigned long long k = s_word[i];
+          if (k != ~0ull && (k & pmask) == prefix) atomicAdd(&s_hist[(int)((k >> shift) & 255ull)], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {                              // first digit whose cumulative count reaches the rank
+          int cum = 0, d = 0;
+          for (; d < 255; ++d) {
+            if (cum + s_hist[d] >= need) break;
+            cum += s_hist[d];
+          }
+          s_pick[0] = d; s_pick[1] = need - cum;
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)s_pick[0] << shift;
+        pmask |= 255ull << shift;
+        need = s_pick[1];
+        __syncthreads();
+      }
+      thr = prefix;                                  // the take-th smallest word (words are unique, every one below all ones)
+    }
+    // ascending order: every thread owns a run of consecutive candidates, an exclusive scan of the runs' counts places them
+    const int C = (M + kPtsThreads - 1) / kPtsThreads;
+    const int i0 = min(tid * C, M), i1 = min(i0 + C, M);
+    auto chosen = [&](int i) -> bool { return cut ? s_word[i] <= thr : (mask == 0 || (s_set[i] & mask)); };
+    int cnt = 0;
+    for (int i = i0; i < i1; ++i) cnt += chosen(i) ? 1 : 0;
+    int inc = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(inc, o);
+      if (lane >= o) inc += v;
+    }
+    __syncthreads();
+    if (lane == 63) s_red[wave] = inc;
+    __syncthreads();
+    int off = base + inc - cnt;
+    for (int w = 0; w < wave; ++w) off += s_red[w];
+    for (int i = i0; i < i1; ++i)
+      if (chosen(i) && off < R) keep[off++] = i;
+    __syncthreads();
+  };
+  select_emit(0, 1, nfg, fg_take, 0);
+  select_emit(1, 2, nbg, bg_take, fg_take);
+  int have = fg_take + bg_take;
+  for (int t = 0; have < R; ++t) {                   // rcnn.py:370-373: pad from ALL candidates, repeats and neither-set rows included
+    const int gap = min(M, R - have);
+    select_emit(2 + t, 0, M, gap, have);
+    have += gap;
+  }
+  __syncthreads();                                   // keep[] (global, written by this workgroup) is complete
+  // ---- rows (rcnn.py:376-395)
+  for (int r = tid; r < R; r += kPtsThreads) {
+    const int i = min(max(keep[r], 0), M - 1);      // (every slot holds a candidate index; the clamp only bounds the reads below)
+    float box[4];
+    const float im = cand_box(i, box);
+    float* ro = g.rois_out + ((long)b * R + r) * 5;
+    float* bt = g.bbox_target + ((long)b * R + r) * D;
+    float* bwp = g.bbox_weight + ((long)b * R + r) * D;
+    for (int c = 0; c < D; ++c) { bt[c] = 0.f; bwp[c] = 0.f; }
+    ro[0] = im;
+    for (int c = 0; c < 4; ++c) ro[1 + c] = box[c];
+    g.label[(long)b * R + r] = pt_label_targets(box, gtb, G, g.bg_thresh_hi, g.num_reg, g.class_agnostic, g.mean, g.stdv, g.bw, bt, bwp);
+  }
+}
+
 #pragma clang fp contract(fast)
 struct OverlapArgs { const double* boxes; const double* query; double* out; int N, K; };
 __global__ __launch_bounds__(256) void bbox_overlaps_kernel(OverlapArgs g) {
@@ -497,6 +687,32 @@ extern "C" int relnet_proposal_target_ex(const float* rois, const float* gt, con
            {weights4[0], weights4[1], weights4[2], weights4[3]}, num_rois};
   proposal_target_kernel<<<dim3((N + Gmax + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(g);
   return check_launch("relnet_proposal_target");
+}
+
+extern "C" int relnet_proposal_target_sample(const float* rois, const float* gt, const int* num_gt, const int* num_rois,
+                                             float* rois_out, float* label, float* bbox_target, float* bbox_weight,
+                                             int* keep_index, int B, int N, int Gmax, int rois_per_image,
+                                             int fg_rois_per_image, double fg_thresh, double bg_thresh_hi, double bg_thresh_lo,
+                                             int append_gt, int num_reg, int class_agnostic, const double* means4,
+                                             const double* stds4, const double* weights4, unsigned long long seed,
+                                             const unsigned long long* seed_dev, void* stream) {
+  RELNET_REQUIRE(rois && gt && num_gt && rois_out && label && bbox_target && bbox_weight && keep_index && means4 && stds4 && weights4,
+                 "relnet_proposal_target_sample: null operand");
+  RELNET_REQUIRE(B > 0 && N >= 0 && Gmax >= 0 && num_reg > 0 && rois_per_image > 0 && fg_rois_per_image >= 0 &&
+                 fg_rois_per_image <= rois_per_image, "relnet_proposal_target_sample: bad shape");
+  RELNET_REQUIRE((long)N + (append_gt ? Gmax : 0) <= kPtsMax,
+                 "relnet_proposal_target_sample: %ld candidates per image, the limit is %d (their words live in LDS)",
+                 (long)N + (append_gt ? Gmax : 0), kPtsMax);
+  PTSArgs g{};
+  g.rois = rois; g.gt = gt; g.num_gt = num_gt; g.num_rois = num_rois;
+  g.rois_out = rois_out; g.label = label; g.bbox_target = bbox_target; g.bbox_weight = bbox_weight; g.keep_index = keep_index;
+  g.N = N; g.Gmax = Gmax; g.R = rois_per_image; g.fg_rois = fg_rois_per_image; g.append_gt = append_gt ? 1 : 0;
+  g.num_reg = num_reg; g.class_agnostic = class_agnostic;
+  g.fg_thresh = fg_thresh; g.bg_thresh_hi = bg_thresh_hi; g.bg_thresh_lo = bg_thresh_lo;
+  for (int c = 0; c < 4; ++c) { g.mean[c] = means4[c]; g.stdv[c] = stds4[c]; g.bw[c] = weights4[c]; }
+  g.seed = seed; g.seed_dev = seed_dev;
+  proposal_target_sample_kernel<<<B, kPtsThreads, 0, (hipStream_t)stream>>>(g);
+  return check_launch("relnet_proposal_target_sample");
 }
 
 extern "C" int relnet_proposal_target(const float* rois, const float* gt, const int* num_gt, float* rois_out,

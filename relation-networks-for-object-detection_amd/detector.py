@@ -81,6 +81,9 @@ class Config(object):
         c.scales = tuple(e.SCALES[0])
         if hasattr(cls, 'batch_rois_ohem'):                          # a TrainConfig
             c.batch_rois_ohem, c.enable_ohem = t.BATCH_ROIS_OHEM, bool(t.ENABLE_OHEM)
+            # TRAIN.BATCH_ROIS counts the rois of a whole BATCH_IMAGES batch (proposal_target.py:60), cfg.batch_rois those of one image
+            c.batch_rois = t.BATCH_ROIS // t.BATCH_IMAGES if t.BATCH_ROIS > 0 else t.BATCH_ROIS
+            c.fg_fraction, c.fg_thresh, c.bg_thresh_lo = float(t.FG_FRACTION), float(t.FG_THRESH), float(t.BG_THRESH_LO)
             c.joint_training = bool(t.JOINT_TRAINING) or not t.LEARN_NMS
             c.lr, c.momentum, c.wd = t.lr, t.momentum, t.wd
             c.rpn_batch_size = t.RPN_BATCH_SIZE

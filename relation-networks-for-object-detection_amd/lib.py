@@ -159,6 +159,7 @@ _SIGNATURES = {
     'relnet_stem_conv7': (C.c_int, [_vp, _vp, _vp, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'relnet_proposal_target': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'relnet_proposal_target_ex': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    'relnet_proposal_target_sample': (C.c_int, [_vp] * 9 + [_i] * 5 + [C.c_double] * 3 + [_i] * 3 + [_vp] * 3 + [C.c_ulonglong, _vp, _vp]),
     'relnet_assign_anchor': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
                                        C.c_double, C.c_double, _i, _i, C.c_ulonglong, _vp, _vp]),
     'relnet_box_annotator_ohem': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -12,17 +12,27 @@ class ProposalTargetOperator(CustomOp):
     def __init__(self, num_classes, batch_images, batch_rois, cfg, fg_fraction):
         super(ProposalTargetOperator, self).__init__()
         self._num_classes, self._batch_images, self._batch_rois, self._cfg = num_classes, batch_images, batch_rois, cfg
-        if batch_rois != -1:
-            raise NotImplementedError("only BATCH_ROIS = -1 (all proposals + gt, no sampling) is on the hot path; "
-                                      "every shipped end2end cfg uses it")
+        self._fg_fraction = fg_fraction
+        self._calls = 0              # forward calls so far: added to cfg['seed'], so every call draws a new sample
 
     def forward(self, is_train, req, in_data, out_data, aux):
+        assert self._batch_rois == -1 or self._batch_rois % self._batch_images == 0, \
+            'batchimages {} must devide batch_rois {}'.format(self._batch_images, self._batch_rois)      # proposal_target.py:45-46
         rois, gt = in_data[0].float(), in_data[1].float()
         if not bool((rois[:, 0] == 0).all()):
             raise AssertionError('Only single item batches are supported')      # proposal_target.py:69
         c = self._cfg
+        br = self._batch_rois
+        kw = {}                      # proposal_target.py:50-55: -1 every proposal and every gt row, -2 every proposal
+        if br not in (-1, -2):       # :56-61: sampled, with (> 0) or without (< -10) the gt rows as candidates
+            per_image = (-br if br < -10 else br) // self._batch_images
+            kw = dict(batch_rois=per_image, fg_fraction=self._fg_fraction, fg_thresh=c['fg_thresh'], bg_thresh_lo=c['bg_thresh_lo'],
+                      append_gt=br > 0, seed=int(c['seed']) + self._calls)
+            self._calls += 1
         r, lab, bt, bw = ops.proposal_target(rois[None], gt[None], None, self._num_classes, c['class_agnostic'],
-                                             c['bg_thresh_hi'], c['means'], c['stds'], c['weights'])
+                                             c['bg_thresh_hi'], c['means'], c['stds'], c['weights'], **kw)
+        if br == -2:                 # the all-rows kernel writes the gt rows behind the N proposals: -2 leaves them out
+            r, lab, bt, bw = (t[:, :rois.shape[0]] for t in (r, lab, bt, bw))
         for ind, val in enumerate([r[0], lab[0], bt[0], bw[0]]):
             self.assign(out_data[ind], req[ind], val)
 
@@ -34,12 +44,15 @@ class ProposalTargetOperator(CustomOp):
 @register('proposal_target')
 class ProposalTargetProp(CustomOpProp):
     """cfg: the reference pickles its whole EasyDict into this attribute (proposal_target.py:107); here a
-    plain dict (or its repr) with class_agnostic / bg_thresh_hi / means / stds / weights."""
+    plain dict (or its repr) with class_agnostic / bg_thresh_hi / means / stds / weights, and for the sampled forms of
+    batch_rois (> 0, < -10: proposal_target.py:56-61) fg_thresh / bg_thresh_lo / seed -- the operator adds its call count
+    to `seed`, so every forward draws a new sample (the reference draws from numpy's global generator)."""
 
     def __init__(self, num_classes, batch_images, batch_rois, cfg='None', fg_fraction='0.25'):
         super(ProposalTargetProp, self).__init__(need_top_grad=False)
         self._num_classes, self._batch_images, self._batch_rois = int(num_classes), int(batch_images), int(batch_rois)
-        d = dict(class_agnostic=True, bg_thresh_hi=0.5, means=(0., 0., 0., 0.), stds=(0.1, 0.1, 0.2, 0.2), weights=(1., 1., 1., 1.))
+        d = dict(class_agnostic=True, bg_thresh_hi=0.5, means=(0., 0., 0., 0.), stds=(0.1, 0.1, 0.2, 0.2), weights=(1., 1., 1., 1.),
+                 fg_thresh=0.5, bg_thresh_lo=0.0, seed=0)
         if cfg not in (None, 'None'):
             if isinstance(cfg, str):
                 import ast
@@ -53,7 +66,8 @@ class ProposalTargetProp(CustomOpProp):
                 cfg = dict(class_agnostic=bool(cfg['CLASS_AGNOSTIC']), bg_thresh_hi=float(t['BG_THRESH_HI']),
                            means=tuple(float(v) for v in t['BBOX_MEANS']) if norm else (0., 0., 0., 0.),
                            stds=tuple(float(v) for v in t['BBOX_STDS']) if norm else (1., 1., 1., 1.),
-                           weights=tuple(float(v) for v in t['BBOX_WEIGHTS']))
+                           weights=tuple(float(v) for v in t['BBOX_WEIGHTS']),
+                           fg_thresh=float(t['FG_THRESH']), bg_thresh_lo=float(t['BG_THRESH_LO']))
             d.update(cfg)
         self._cfg, self._fg_fraction = d, float(fg_fraction)
 
@@ -65,7 +79,14 @@ class ProposalTargetProp(CustomOpProp):
 
     def infer_shape(self, in_shape):
         rpn_rois_shape, gt_boxes_shape = in_shape[0], in_shape[1]
-        rois = rpn_rois_shape[0] + gt_boxes_shape[0]                     # BATCH_ROIS = -1 (proposal_target.py:117-118)
+        if self._batch_rois == -1:                                       # proposal_target.py:120-127
+            rois = rpn_rois_shape[0] + gt_boxes_shape[0]
+        elif self._batch_rois == -2:
+            rois = rpn_rois_shape[0]
+        elif self._batch_rois < -10:
+            rois = -self._batch_rois
+        else:
+            rois = self._batch_rois
         return [rpn_rois_shape, gt_boxes_shape], [(rois, 5), (rois,), (rois, self._num_classes * 4), (rois, self._num_classes * 4)]
 
     def create_operator(self, ctx, shapes, dtypes):

@@ -1003,18 +1003,49 @@ def _d4(v):
 
 
 def proposal_target(rois, gt_boxes, num_gt=None, num_reg=2, class_agnostic=True, bg_thresh_hi=0.5,
-                    means=(0.0, 0.0, 0.0, 0.0), stds=(0.1, 0.1, 0.2, 0.2), weights=(1.0, 1.0, 1.0, 1.0), num_rois=None):
+                    means=(0.0, 0.0, 0.0, 0.0), stds=(0.1, 0.1, 0.2, 0.2), weights=(1.0, 1.0, 1.0, 1.0), num_rois=None,
+                    batch_rois=None, fg_rois=None, fg_thresh=0.5, bg_thresh_lo=0.0, append_gt=True, seed=0, seed_dev=None,
+                    want_index=False, fg_fraction=0.25):
     """rois [B,N,5], gt_boxes [B,Gmax,5] (x1,y1,x2,y2,cls), num_gt [B] int32 (default: all Gmax valid)
     -> rois_out [B,N+Gmax,5], label [B,N+Gmax], bbox_target / bbox_weight [B,N+Gmax,4*num_reg]
     (BATCH_ROIS = -1 semantics; rows past N + num_gt[b] carry label -1 and zero weights).
     num_rois [B] int32 (optional): only the first num_rois[b] input rows are proposals; the padded rows come out with a
-    zero box, label -1 and zero weights."""
+    zero box, label -1 and zero weights.
+
+    batch_rois = R > 0: the sampled minibatch of core/rcnn.py:329-397 (relnet_proposal_target_sample, include/relnet_hip.h
+    states the rule): R rows per image, at most fg_rois (default round-half-even(fg_fraction * R), proposal_target.py:58,61)
+    of them with overlap >= fg_thresh, the rest from [bg_thresh_lo, bg_thresh_hi), padded to R; candidates = the proposals
+    (+ the gt rows with append_gt); the random subsets are selected by `seed` (+ the device int64 word `seed_dev`, e.g. a step
+    counter advanced inside a captured graph).  Outputs have R rows; with want_index a fifth output keep_index [B,R] int32
+    names the candidate each row was taken from."""
     _chk(rois, gt_boxes, num_gt, num_rois)
     B, N, _ = rois.shape
     G = gt_boxes.shape[1]
     dev = rois.device
     if num_gt is None:
         num_gt = torch.full((B,), G, device=dev, dtype=torch.int32)
+    if batch_rois is not None:
+        import ctypes
+        R = int(batch_rois)
+        if R <= 0:
+            raise ValueError("proposal_target: batch_rois is the number of sampled rois per image (> 0), got %d" % R)
+        if fg_rois is None:
+            fg_rois = int(round(fg_fraction * R))       # (Python's round is numpy's: half to even)
+        if G == 0:                   # images without any box: one (ignored) gt slot keeps the buffer non-empty
+            gt_boxes = torch.zeros((B, 1, 5), device=dev, dtype=torch.float32)
+            num_gt, G = torch.zeros((B,), device=dev, dtype=torch.int32), 1
+        assert rois.dtype == torch.float32 and gt_boxes.dtype == torch.float32
+        ro = torch.empty((B, R, 5), device=dev, dtype=torch.float32)
+        lab = torch.empty((B, R), device=dev, dtype=torch.float32)
+        bt = torch.empty((B, R, 4 * num_reg), device=dev, dtype=torch.float32)
+        bw = torch.empty((B, R, 4 * num_reg), device=dev, dtype=torch.float32)
+        keep = torch.empty((B, R), device=dev, dtype=torch.int32)
+        _lib.call('relnet_proposal_target_sample', rois.contiguous().data_ptr(), gt_boxes.contiguous().data_ptr(), num_gt.data_ptr(),
+                  _ptr(num_rois), ro.data_ptr(), lab.data_ptr(), bt.data_ptr(), bw.data_ptr(), keep.data_ptr(), B, N, G, R,
+                  int(fg_rois), float(fg_thresh), float(bg_thresh_hi), float(bg_thresh_lo), int(bool(append_gt)), num_reg,
+                  int(class_agnostic), _d4(means), _d4(stds), _d4(weights), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)),
+                  _ptr(seed_dev), _stream())
+        return (ro, lab, bt, bw, keep) if want_index else (ro, lab, bt, bw)
     R = N + G
     ro = torch.empty((B, R, 5), device=dev, dtype=torch.float32)
     lab = torch.empty((B, R), device=dev, dtype=torch.float32)

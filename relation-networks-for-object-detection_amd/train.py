@@ -35,6 +35,11 @@ from .operator_py.proposal import generate_anchors, propose_batch
 class TrainConfig(Config):
     rpn_batch_size = 256          # TRAIN.RPN_BATCH_SIZE
     batch_rois_ohem = 128         # TRAIN.BATCH_ROIS_OHEM
+    batch_rois = -1               # -1: every proposal + the gt rows (TRAIN.BATCH_ROIS of the shipped yamls).  R > 0: R sampled rois PER IMAGE
+                                  # (TRAIN.BATCH_ROIS // TRAIN.BATCH_IMAGES; core/rcnn.py:329-397 sample_rois), plain heads only
+    fg_fraction = 0.25            # TRAIN.FG_FRACTION: at most round(fg_fraction * batch_rois) sampled rois are foreground
+    fg_thresh = 0.5               # TRAIN.FG_THRESH
+    bg_thresh_lo = 0.0            # TRAIN.BG_THRESH_LO (background = overlap in [bg_thresh_lo, BG_THRESH_HI 0.5))
     lr = 0.0005
     momentum = 0.9
     wd = 0.0005
@@ -107,6 +112,22 @@ def check_deterministic(cfg):
         raise ValueError("deterministic training does not cover cfg.dcn: deformable_psroi_pool_bwd and deformable_col2im accumulate with float atomics")
     if getattr(cfg, 'roi_align', False):
         raise ValueError("deterministic training does not cover cfg.roi_align: roi_align_bwd accumulates with float atomics")
+
+
+def check_batch_rois(cfg):
+    """cfg.batch_rois is -1 (every proposal + the gt rows) or the number of sampled rois per image.  The relation modules and the learn-NMS
+    head take the first RPN_POST_NMS_TOP_N rows of an image as attention keys / ranked proposals (nongt_dim, symbols/...:220-262): a sampled
+    minibatch has no such rows, so those graphs are refused by name (the reference's relation yamls all set BATCH_ROIS -1 for this reason)."""
+    r = int(getattr(cfg, 'batch_rois', -1))
+    if r == -1:
+        return
+    if r <= 0:
+        raise ValueError("cfg.batch_rois is -1 or the sampled rois per image (TRAIN.BATCH_ROIS // TRAIN.BATCH_IMAGES > 0), got %d; the -2 and "
+                         "< -10 forms of BATCH_ROIS exist on the proposal_target operator only" % r)
+    for flag in ('relation', 'learn_nms'):
+        if getattr(cfg, flag, flag == 'relation'):
+            raise ValueError("cfg.%s with batch_rois = %d: the attention keys are the first RPN_POST_NMS_TOP_N rows of every image, which a "
+                             "sampled minibatch does not keep -- these graphs need BATCH_ROIS = -1" % (flag, r))
 
 
 class _Flat(object):
@@ -202,6 +223,7 @@ class Trainer(object):
         self.cfg = cfg or TrainConfig()
         check_pooling(self.cfg)
         check_deterministic(self.cfg)
+        check_batch_rois(self.cfg)
         check_box_head(self.cfg, params)
         self.device, self.im_hw = device, im_hw
         c = self.cfg
@@ -501,6 +523,23 @@ class Trainer(object):
         self._anchor_step += 1
         return out
 
+    def roi_targets(self, rois, gt_boxes, num_gt, num_rois=None, advance=False):
+        """operator_py/proposal_target.py:44-93 on the device: labels and regression targets of the step's rois.  cfg.batch_rois -1: every
+        proposal + the gt rows (today's launch).  cfg.batch_rois = R > 0: the sampled minibatch (core/rcnn.py:329-397), keyed like the anchor
+        sampler by the trainer's seed + the device step counter AS IT STANDS when this launch runs (after `rpn_targets` of the same step, which
+        advances it); advance=True advances it here, for a step in which `rpn_targets` does not run -- so every step, and every replay of a
+        captured one, draws a new sample.  Returns (rois_t, label, bbox_target, bbox_weight, keep_index or None)."""
+        c = self.cfg
+        R = int(getattr(c, 'batch_rois', -1))
+        if R <= 0:
+            return ops.proposal_target(rois, gt_boxes, num_gt, num_rois=num_rois, **box_target_layout(c)) + (None,)
+        o = ops.proposal_target(rois, gt_boxes, num_gt, num_rois=num_rois, batch_rois=R, fg_fraction=c.fg_fraction, fg_thresh=c.fg_thresh,
+                                bg_thresh_lo=c.bg_thresh_lo, seed=getattr(c, 'seed', 0) * self._world + self._rank,
+                                seed_dev=self._anchor_step, want_index=True, **box_target_layout(c))
+        if advance:
+            self._anchor_step += 1
+        return o
+
     def forward_backward(self, *args, **kwargs):
         """One forward + backward pass (arguments: see `_forward_backward_impl` of the trainer class).  While it runs, bias-gradient column sums
         and weight-gradient products are queued on the trainer and launched grouped when a gradient bucket completes (`_flush_wgrads`)."""
@@ -512,7 +551,9 @@ class Trainer(object):
     def _forward_backward_impl(self, data, im_info, gt_boxes, rpn_label=None, rpn_bbox_target=None, rpn_bbox_weight=None, num_gt=None):
         """data [B,3,H,W] fp32 or [B,H,W,3] uint8 BGR HWC (Backbone.forward); gt_boxes [B,G,5]; rpn_label [B, A*h*w] ((a,y,x) order), rpn_bbox_target / weight
         [B, 4A, h, w] (lib/rpn/rpn.py:assign_anchor layouts) -- or None: computed on the device from gt_boxes
-        (`rpn_targets`).  Accumulates gradients into the flat buffers and returns the loss values (reference metric names)."""
+        (`rpn_targets`).  Accumulates gradients into the flat buffers and returns the loss values (reference metric names).
+        With cfg.batch_rois > 0 the head runs on the sampled rows only (`roi_targets`) and `out` also carries `proposals` [B,N,5] (the RPN's
+        output the sample was drawn from) and `keep_index` [B,R] (the candidate -- proposal, or N + gt row -- behind every row)."""
         c = self.cfg
         B = data.shape[0]
         self._grad_buckets().reset()
@@ -563,8 +604,13 @@ class Trainer(object):
                                     c.rpn_pre_nms_top_n, c.rpn_post_nms_top_n, c.rpn_nms_thresh, c.rpn_min_size,
                                     im_hw=self.im_hw, softmax_pairs=True)
             N = rois.shape[1]
-            rois_t, label, bbox_target, bbox_weight = ops.proposal_target(rois, gt_boxes, num_gt, **box_target_layout(c))
+            # (a step with host-made anchor targets never ran rpn_targets: the sampler advances the step counter itself)
+            rois_t, label, bbox_target, bbox_weight, keep = self.roi_targets(rois, gt_boxes, num_gt, advance=early is None)
             R = rois_t.shape[1]
+            if keep is not None:    # sampled minibatch: R rows, none of them a key row (plain heads only, check_batch_rois)
+                N = R
+                br['keep_index'] = out['keep_index'] = keep
+                out['proposals'] = br['proposals'] = rois
             br.update(r=r, d_rpn=d_rpn, rois_t=rois_t, label=label, bbox_target=bbox_target, bbox_weight=bbox_weight, N=N, R=R)
             if rpn_bwd_side:
                 br['ev'] = torch.cuda.Event()
@@ -793,6 +839,8 @@ class Trainer(object):
         else:       # ENABLE_OHEM false (symbols/..._learn_nms_1024_...:232-241): every roi counts (padding rows of a short proposal list keep label -1
             labels_ohem, weights_ohem = label, bbox_weight          # and are ignored), the box loss is scaled by 1 / 300 (BATCH_ROIS < 0)
             box_norm = 300
+            if getattr(c, 'batch_rois', -1) > 0:                    # a sampled minibatch: 1 / BATCH_ROIS per image (resnet_v1_101_rcnn.py:154-158)
+                box_norm = c.batch_rois
         cls_prob, d_cls = losses.softmax_output(cls_score.view(B * R, -1), labels_ohem.reshape(-1), use_ignore=True, ignore_label=-1.0, group=R)
         d_cls = d_cls.view(B, R, -1)
         l1, d_bbox = losses.smooth_l1_loss(bbox_pred, bbox_target, weights_ohem, 1.0, 1.0 / box_norm)
@@ -1429,17 +1477,24 @@ class FPNTrainer(Trainer):
         # ---- rois: labels / targets, then level dispatch (non-gt rows first, gt rows after)
         rois5 = torch.cat([torch.zeros((B, N, 1), device=proposals.device), proposals], 2)
         rois5[:, :, 0] = torch.arange(B, device=proposals.device, dtype=torch.float32).view(B, 1)
-        rois_t, label, bbox_target, bbox_weight = ops.proposal_target(rois5.contiguous(), gt_boxes, num_gt, num_rois=num_proposals, **box_target_layout(self.cfg))
+        # (this trainer never runs rpn_targets: a sampled minibatch advances the device step counter itself)
+        rois_t, label, bbox_target, bbox_weight, keep = self.roi_targets(rois5.contiguous(), gt_boxes, num_gt, num_rois=num_proposals, advance=True)
         R = rois_t.shape[1]
         key_count = None
-        if num_proposals is not None:
-            ra, la, pa, _, key_count = ops.fpn_roi_dispatch(rois_t[:, :N].contiguous(), n_valid=num_proposals)
+        if keep is not None:        # sampled minibatch (resnet_v1_101_rcnn_fpn.py:1172-1179): R rows drawn from the num_proposals real rows + the gt
+            N = R                   # rows -- no padded row among them, no key rows (plain heads only, check_batch_rois): one dispatch
+            rois_s, level, pa, _ = ops.fpn_roi_dispatch(rois_t)
+            perm = pa.long()
+            out['keep_index'] = keep
         else:
-            ra, la, pa, _ = ops.fpn_roi_dispatch(rois_t[:, :N].contiguous())
-        rb, lb, pb, _ = ops.fpn_roi_dispatch(rois_t[:, N:].contiguous())
-        rois_s = torch.cat([ra, rb], 1).contiguous()
-        level = torch.cat([la, lb], 1).contiguous()
-        perm = torch.cat([pa, pb + N], 1).long()
+            if num_proposals is not None:
+                ra, la, pa, _, key_count = ops.fpn_roi_dispatch(rois_t[:, :N].contiguous(), n_valid=num_proposals)
+            else:
+                ra, la, pa, _ = ops.fpn_roi_dispatch(rois_t[:, :N].contiguous())
+            rb, lb, pb, _ = ops.fpn_roi_dispatch(rois_t[:, N:].contiguous())
+            rois_s = torch.cat([ra, rb], 1).contiguous()
+            level = torch.cat([la, lb], 1).contiguous()
+            perm = torch.cat([pa, pb + N], 1).long()
         gat = lambda t: torch.gather(t, 1, perm.view(B, R, *([1] * (t.dim() - 2))).expand(B, R, *t.shape[2:]))
         label, bbox_target, bbox_weight = gat(label), gat(bbox_target).contiguous(), gat(bbox_weight).contiguous()
         nchw = lambda t: t.permute(0, 3, 1, 2)
