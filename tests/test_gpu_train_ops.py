@@ -196,13 +196,14 @@ def test_wgrad_tn_matches_float64(case):
             base = torch.randn(want.shape[0], want.shape[1] + 24, generator=g).cuda()          # accumulate into a view of a wider buffer
             out = base[:, 8:8 + want.shape[1]]
             before = out.clone()
+            guard = torch.cat([base[:, :8], base[:, 8 + want.shape[1]:]], 1).clone()          # the columns on both sides of the view, before the launch
             ops.wgrad_tn(dyb, xk, out=out, row_scale=scale, cout=want.shape[0], conv=conv)
             got = (out - before).double().cpu()
         finally:
             L.load().relnet_wgrad_debug_plain(0)
         err = (got - want).abs().max().item() / want.abs().max().item()
         assert err <= 2e-5, (case, plain, err)              # fp32 accumulation of exact bf16 products
-        assert torch.equal(base[:, :8], base[:, :8]) and torch.isfinite(base).all()
+        assert torch.equal(torch.cat([base[:, :8], base[:, 8 + want.shape[1]:]], 1), guard) and torch.isfinite(base).all()
     fresh = ops.wgrad_tn(dyb, xk, row_scale=scale, cout=want.shape[0], conv=conv)
     assert (fresh.double().cpu() - want).abs().max().item() <= 2e-5 * want.abs().max().item()
     # the same layer inside a grouped launch with two other layers (stream-K shares cut across layer boundaries), and with
