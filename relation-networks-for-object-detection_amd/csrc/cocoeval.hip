@@ -11,6 +11,7 @@ constexpr int kCocoMatchThreads = 1024;      // the (category, area, threshold) 
 constexpr int kCocoMaxSlots = 2048;        // detection slots per image (LDS: 16 bytes per slot)
 constexpr int kCocoMaxPairs = 64;          // area ranges x IoU thresholds (one lane each in the accumulation)
 constexpr int kCocoMaxDetsLen = 4;         // entries of Params.maxDets
+constexpr int kCocoMaxAreas = 7;           // area ranges (gt_flags: bit 0 iscrowd, bit 1 + a ignored in range a)
 constexpr int kSortTile = 2048;            // elements per workgroup of one radix pass
 constexpr int kSortThreads = 256;          // = radix
 
@@ -412,10 +413,12 @@ extern "C" int relnet_coco_match(const void* det, int det_dtype, const int* num_
                  slot_rank && slot_code, "relnet_coco_match: null operand");
   RELNET_REQUIRE(gt_cap == 0 || (gt_box && gt_flags && gtm_scratch), "relnet_coco_match: null ground-truth operand");
   RELNET_REQUIRE(det_dtype == 0 || det_dtype == 1, "relnet_coco_match: detections must be float32 (0) or float64 (1)");
-  RELNET_REQUIRE(B > 0 && S_in > 0 && S_in <= S && S <= kCocoMaxSlots && n_images > 0 && n_classes > 0 && K > 0 && A > 0 &&
-                 A <= 7 && T > 0 && A * T <= kCocoMaxPairs && gt_cap >= 0 && max_det > 0,
-                 "relnet_coco_match: bad shape (B %d, S_in %d, S %d, n_images %d, K %d, A %d, T %d)", B, S_in, S, n_images, K,
-                 A, T);
+  RELNET_REQUIRE(B > 0 && S_in > 0 && S_in <= S && n_images > 0 && n_classes > 0 && K > 0 && A > 0 && T > 0 && gt_cap >= 0 &&
+                 max_det > 0, "relnet_coco_match: bad shape (B %d, S_in %d, S %d, n_images %d, K %d, A %d, T %d)", B, S_in, S,
+                 n_images, K, A, T);
+  RELNET_REQUIRE(S <= kCocoMaxSlots, "relnet_coco_match: %d detection slots per image, at most %d", S, kCocoMaxSlots);
+  RELNET_REQUIRE(A <= kCocoMaxAreas && A * T <= kCocoMaxPairs, "relnet_coco_match: %d area ranges (at most %d), %d (area, IoU) "
+                 "pairs (at most %d)", A, kCocoMaxAreas, A * T, kCocoMaxPairs);
   CocoMatchArgs g;
   g.det = det; g.num_det = num_det; g.image_pos = image_pos; g.class_to_cat = class_to_cat; g.gt_off = gt_off;
   g.gt_box = gt_box; g.gt_flags = gt_flags; g.iou_thr = iou_thr; g.area_rng = area_rng; g.gtm = (unsigned char*)gtm_scratch;
@@ -433,8 +436,10 @@ extern "C" int relnet_coco_accumulate(const int* slot_cat, const double* slot_sc
                                       int T, int R, int M, int max_det_host, void* stream) {
   RELNET_REQUIRE(slot_cat && slot_score && slot_rank && slot_code && npig && rec_thr && max_dets && precision && recall &&
                  workspace, "relnet_coco_accumulate: null operand");
-  RELNET_REQUIRE(n_slots > 0 && n_slots < (1l << 31) && K > 0 && K < 65535 && A > 0 && T > 0 && A * T <= kCocoMaxPairs &&
-                 R > 0 && M > 0 && M <= kCocoMaxDetsLen && max_det_host > 0, "relnet_coco_accumulate: bad shape");
+  RELNET_REQUIRE(n_slots > 0 && n_slots < (1l << 31) && K > 0 && K < 65535 && A > 0 && T > 0 && R > 0 && M > 0 &&
+                 max_det_host > 0, "relnet_coco_accumulate: bad shape");
+  RELNET_REQUIRE(A * T <= kCocoMaxPairs && M <= kCocoMaxDetsLen, "relnet_coco_accumulate: %d (area, IoU) pairs (at most %d), "
+                 "%d maxDets (at most %d)", A * T, kCocoMaxPairs, M, kCocoMaxDetsLen);
   const int AT = A * T;
   const long need = relnet_coco_accumulate_workspace_bytes(n_slots, K, AT);
   RELNET_REQUIRE(workspace_bytes >= need, "relnet_coco_accumulate: workspace of %ld bytes, %ld needed", workspace_bytes, need);

@@ -15,6 +15,7 @@ from test_dataset import make_dataset  # noqa: E402
 
 import relnet_amd  # noqa: F401,E402
 from relnet_amd.dataset import cocoeval, device_eval as DE  # noqa: E402
+from eval_edge_cases import synthetic_problem as _problem  # noqa: E402  (shared with the edge suite)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,72 +50,6 @@ def test_golden_case_equals_reference_pycocotools_and_cocoeval():
     assert np.array_equal(dev.eval['precision'], g['precision']) and np.array_equal(dev.eval['recall'], g['recall'])
     assert np.array_equal(dev.stats, g['stats'])
     _same(dev, host)
-
-
-def _problem(seed, n_images=24):
-    """Crowd and ignored ground truth, areas exactly 32^2 / 96^2, scores tied inside and across images, images without ground
-    truth or without detections, a category without detections, one whose ground truth is all ignored, one with nothing,
-    150 detections in one (image, category) and 300 ground-truth boxes in another."""
-    rng = np.random.default_rng(seed)
-    cats = [2, 5, 9, 11, 13]                 # 9: no detections; 11: every box crowd or ignored; 13: nothing at all
-    img_ids = [1000 + 3 * i for i in range(n_images)]
-    gts, dts = [], []
-
-    def box(scale):
-        w, h = float(rng.uniform(0.5, 1.5) * scale), float(rng.uniform(0.5, 1.5) * scale)
-        return [float(rng.uniform(0, 500)), float(rng.uniform(0, 400)), w, h]
-
-    def det_near(b, img, cat):
-        j = rng.normal(0, 0.12, 4)
-        dts.append(dict(image_id=img, category_id=cat, score=float(np.round(rng.random(), 1)),
-                        bbox=[b[0] + j[0] * b[2], b[1] + j[1] * b[3], b[2] * float(np.exp(j[2])), b[3] * float(np.exp(j[3]))]))
-
-    for i, img in enumerate(img_ids):
-        if i % 7 == 3:                       # no ground truth, detections only
-            for _ in range(5):
-                det_near(box(40), img, 2)
-            continue
-        for cat in (2, 5, 9, 11):
-            for _ in range(int(rng.integers(0, 6))):
-                b = box(float(np.exp(rng.uniform(np.log(10), np.log(200)))))
-                gd = dict(image_id=img, category_id=cat, bbox=b)
-                r = rng.random()
-                if cat == 11:
-                    gd['iscrowd' if r < 0.5 else 'ignore'] = 1
-                elif r < 0.1:
-                    gd['iscrowd'] = 1
-                elif r < 0.2:
-                    gd['ignore'] = 1
-                elif r < 0.3:
-                    gd['area'] = float(32 ** 2)
-                elif r < 0.4:
-                    gd['area'] = float(96 ** 2)
-                gts.append(gd)
-                if cat != 9 and i % 5 != 1:  # images i % 5 == 1: no detections
-                    for _ in range(int(rng.integers(0, 4))):
-                        det_near(b, img, cat)
-            if cat != 9 and i % 5 != 1:
-                for _ in range(int(rng.integers(0, 3))):
-                    dts.append(dict(image_id=img, category_id=cat, score=float(np.round(rng.random() * 0.7, 1)), bbox=box(50)))
-    # 150 detections in one (image, category): maxDets truncation at 100
-    img = img_ids[2]
-    base = [g for g in gts if g['image_id'] == img and g['category_id'] == 5 and not g.get('iscrowd') and not g.get('ignore')]
-    for k in range(150):
-        b = base[k % len(base)]['bbox'] if base and k % 3 == 0 else box(60)
-        det_near(b, img, 5)
-    # 300 ground-truth boxes in one (image, category)
-    img = img_ids[4]
-    for k in range(300):
-        b = [float(10 * (k % 30)), float(12 * (k // 30)), float(rng.uniform(8, 40)), float(rng.uniform(8, 40))]
-        gd = dict(image_id=img, category_id=2, bbox=b)
-        if k % 17 == 0:
-            gd['iscrowd'] = 1
-        gts.append(gd)
-        if k % 2 == 0:
-            det_near(b, img, 2)
-    for i, g in enumerate(gts):
-        g['id'] = i + 1
-    return gts, dts, img_ids, cats
 
 
 @pytest.mark.parametrize('seed', [0, 1, 2])
