@@ -4,6 +4,7 @@
 // Every float64 expression is evaluated in numpy's order with contraction off, so the precision and recall arrays are
 // bit-identical to dataset/cocoeval.py.
 #include "common.h"
+#include "ordering.h"
 
 namespace relnet {
 
@@ -71,11 +72,8 @@ __device__ __forceinline__ double coco_iou(double dx, double dy, double dw, doub
 
 // Sort key of a score for numpy's argsort(-scores, kind='mergesort'): descending, -0.0 tied with 0.0, NaN after every number.
 __device__ __forceinline__ unsigned long long desc_score_key(double s) {
-  if (s != s) return ~0ull;                                  // NaN: numpy sorts it last
-  if (s == 0.0) s = 0.0;
-  unsigned long long u = (unsigned long long)__double_as_longlong(s);
-  u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);          // ascending order of s
-  return ~u;                                                 // descending (-inf: 0xfff0...0, below NaN)
+  const unsigned long long u = order_key(s == 0.0 ? 0.0 : s);     // ascending order of s
+  return s != s ? ~0ull : ~u;                                // descending (-inf: 0xfff0...0, below NaN); NaN: numpy sorts it last
 }
 
 // One workgroup per batch image.  LDS: category position and score of every row, then the rows in (category, -score, row)

@@ -37,7 +37,18 @@ __device__ __forceinline__ int mfma32_row(int r, int lane) {
   return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
 }
 
+// One element of a "float or bf16 bits" tensor (T = float | unsigned short), as float.
+template <typename T> __device__ __forceinline__ float ldf(const T* p);
+template <> __device__ __forceinline__ float ldf<float>(const float* p) { return *p; }
+template <> __device__ __forceinline__ float ldf<unsigned short>(const unsigned short* p) { return bf2f(*p); }
+template <typename T> __device__ __forceinline__ void stf(T* p, float v);
+template <> __device__ __forceinline__ void stf<float>(float* p, float v) { *p = v; }
+template <> __device__ __forceinline__ void stf<unsigned short>(unsigned short* p, float v) { *p = f2bf(v); }
+
 }  // namespace relnet
+
+// dtype codes shared by the whole C-ABI
+enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
 
 // Error plumbing of the C-ABI: every entry point returns 0 or a negative code and
 // records a message retrievable with relnet_last_error().

@@ -18,21 +18,12 @@
 
 namespace relnet {
 
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
-
 struct DeformColArgs {
   const void* data; long ds_b, ds_c, ds_h, ds_w;        // [B,C,H,W] element strides
   const float* offset; long fs_b, fs_c, fs_h, fs_w;     // [B, 2*KH*KW*DG, Ho, Wo]
   void* col; long col_ld;                               // [B*Ho*Wo][col_ld], K = KH*KW*C used
   int B, C, H, W, Ho, Wo, KH, KW, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, DG;
 };
-
-template <typename T> __device__ __forceinline__ float dld(const T* p);
-template <> __device__ __forceinline__ float dld<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float dld<unsigned short>(const unsigned short* p) { return bf2f(*p); }
-template <typename T> __device__ __forceinline__ void dst(T* p, float v);
-template <> __device__ __forceinline__ void dst<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void dst<unsigned short>(unsigned short* p, float v) { *p = f2bf(v); }
 
 #pragma clang fp contract(off)
 
@@ -81,14 +72,14 @@ __global__ __launch_bounds__(256) void deformable_im2col_kernel(DeformColArgs g)
     float val = 0.f;
     if (t.inside) {
       const TIN* p = (const TIN*)g.data + (long)b * g.ds_b + (long)c * g.ds_c;
-      const float v1 = dld<TIN>(p + (long)t.ya * g.ds_h + (long)t.xa * g.ds_w);
-      const float v2 = dld<TIN>(p + (long)t.ya * g.ds_h + (long)t.xb * g.ds_w);
-      const float v3 = dld<TIN>(p + (long)t.yb * g.ds_h + (long)t.xa * g.ds_w);
-      const float v4 = dld<TIN>(p + (long)t.yb * g.ds_h + (long)t.xb * g.ds_w);
+      const float v1 = ldf<TIN>(p + (long)t.ya * g.ds_h + (long)t.xa * g.ds_w);
+      const float v2 = ldf<TIN>(p + (long)t.ya * g.ds_h + (long)t.xb * g.ds_w);
+      const float v3 = ldf<TIN>(p + (long)t.yb * g.ds_h + (long)t.xa * g.ds_w);
+      const float v4 = ldf<TIN>(p + (long)t.yb * g.ds_h + (long)t.xb * g.ds_w);
       val = t.w1 * v1 + t.w2 * v2 + t.w3 * v3 + t.w4 * v4;
     }
     const long row = ((long)b * g.Ho + ho) * g.Wo + wo;
-    dst<TCOL>((TCOL*)g.col + row * g.col_ld + (long)tap * g.C + c, val);
+    stf<TCOL>((TCOL*)g.col + row * g.col_ld + (long)tap * g.C + c, val);
   }
 }
 
@@ -200,16 +191,16 @@ __global__ __launch_bounds__(256) void deformable_psroi_pool_fwd_kernel(PsroiArg
         h = fminf(fmaxf(h, 0.f), (float)g.H - 1.f);
         const int x1 = (int)floorf(w), x2 = (int)ceilf(w), y1 = (int)floorf(h), y2 = (int)ceilf(h);
         const float dx = w - (float)x1, dy = h - (float)y1;
-        const float v11 = dld<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
-        const float v12 = dld<T>(pc + (long)y2 * g.ds_h + (long)x1 * g.ds_w);
-        const float v21 = dld<T>(pc + (long)y1 * g.ds_h + (long)x2 * g.ds_w);
-        const float v22 = dld<T>(pc + (long)y2 * g.ds_h + (long)x2 * g.ds_w);
+        const float v11 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
+        const float v12 = ldf<T>(pc + (long)y2 * g.ds_h + (long)x1 * g.ds_w);
+        const float v21 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x2 * g.ds_w);
+        const float v22 = ldf<T>(pc + (long)y2 * g.ds_h + (long)x2 * g.ds_w);
         const float val = (1.f - dx) * (1.f - dy) * v11 + (1.f - dx) * dy * v12 + dx * (1.f - dy) * v21 + dx * dy * v22;
         sum = sum + val;
         ++count;
       }
     const long o = (long)n * g.os_r + (long)ctop * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw;
-    dst<T>((T*)g.out + o, count == 0 ? 0.f : sum / (float)count);
+    stf<T>((T*)g.out + o, count == 0 ? 0.f : sum / (float)count);
     if (g.top_count) g.top_count[o] = (float)count;
   }
 }
@@ -413,10 +404,10 @@ __global__ __launch_bounds__(256) void deformable_col2im_kernel(DeformBwdArgs a)
     float doh = 0.f, dow = 0.f;
     if (live && t.inside) {
       const TIN* p = (const TIN*)g.data + (long)b * g.ds_b + (long)c * g.ds_c;
-      const float v1 = dld<TIN>(p + (long)t.ya * g.ds_h + (long)t.xa * g.ds_w);
-      const float v2 = dld<TIN>(p + (long)t.ya * g.ds_h + (long)t.xb * g.ds_w);
-      const float v3 = dld<TIN>(p + (long)t.yb * g.ds_h + (long)t.xa * g.ds_w);
-      const float v4 = dld<TIN>(p + (long)t.yb * g.ds_h + (long)t.xb * g.ds_w);
+      const float v1 = ldf<TIN>(p + (long)t.ya * g.ds_h + (long)t.xa * g.ds_w);
+      const float v2 = ldf<TIN>(p + (long)t.ya * g.ds_h + (long)t.xb * g.ds_w);
+      const float v3 = ldf<TIN>(p + (long)t.yb * g.ds_h + (long)t.xa * g.ds_w);
+      const float v4 = ldf<TIN>(p + (long)t.yb * g.ds_h + (long)t.xb * g.ds_w);
       // w1 = hh hw, w2 = hh lw, w3 = lh hw, w4 = lh lw with hh = 1 - lh, hw = 1 - lw; lh, lw move with the offsets
       // (a clamped axis has ya == yb / xa == xb, so its difference below vanishes like the reference's :199-210)
       const float hw = t.w1 + t.w3, lw = t.w2 + t.w4, hh = t.w1 + t.w2, lh = t.w3 + t.w4;
@@ -522,7 +513,7 @@ __global__ __launch_bounds__(256) void deformable_col2im_gather_kernel(DeformBwd
       float v[4][CPL];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if constexpr (CPL == 1) v[u][0] = dld<TCOL>(src_p[u]);
+        if constexpr (CPL == 1) v[u][0] = ldf<TCOL>(src_p[u]);
         else if constexpr (sizeof(TCOL) == 4) { const float2 q = *(const float2*)src_p[u]; v[u][0] = q.x; v[u][1] = q.y; }
         else { const unsigned int q = *(const unsigned int*)src_p[u]; v[u][0] = __uint_as_float(q << 16); v[u][1] = __uint_as_float(q & 0xffff0000u); }
       }
@@ -638,7 +629,7 @@ __global__ __launch_bounds__(256) void deformable_col2im_far_kernel(DeformBwdArg
       const int sb = __shfl(b, src, 64), sd = __shfl(dgi, src, 64), st = __shfl(tap, src, 64);
       const long srow = __shfl(row, src, 64);
       for (int c = sd * cpg + lane; c < (sd + 1) * cpg; c += 64) {
-        const float gv = dld<TCOL>((const TCOL*)a.dcol + srow * a.dcol_ld + (long)st * g.C + c);
+        const float gv = ldf<TCOL>((const TCOL*)a.dcol + srow * a.dcol_ld + (long)st * g.C + c);
         float* gd = a.grad_data + (long)sb * a.gs_b + (long)c * a.gs_c;
         atomicAdd(gd + (long)ya * a.gs_h + (long)xa * a.gs_w, w1 * gv);
         atomicAdd(gd + (long)ya * a.gs_h + (long)xb * a.gs_w, w2 * gv);
@@ -734,7 +725,7 @@ __global__ __launch_bounds__(256) void deformable_psroi_pool_bwd_c4_kernel(Psroi
         const int c = ctop0 + cc * ocs;                   // (group_size 1: input channel = output channel)
         const T* pc = (const T*)g.data + (long)q.b * g.ds_b + (long)c * g.ds_c;
         float* gd = a.grad_data + (long)q.b * a.gs_b + (long)c * a.gs_c;
-        const float diff = dld<T>((const T*)a.grad_out + (long)n * a.go_r + (long)c * a.go_c + (long)ph * a.go_ph + (long)pw * a.go_pw) / (float)count;
+        const float diff = ldf<T>((const T*)a.grad_out + (long)n * a.go_r + (long)c * a.go_c + (long)ph * a.go_ph + (long)pw * a.go_pw) / (float)count;
         if (!a.no_data) {
 #pragma unroll
           for (int ky = 0; ky < 8; ++ky) {
@@ -758,8 +749,8 @@ __global__ __launch_bounds__(256) void deformable_psroi_pool_bwd_c4_kernel(Psroi
               h = fminf(fmaxf(h, 0.f), (float)g.H - 1.f);
               const int x0 = (int)floorf(w), x1 = (int)ceilf(w), y0 = (int)floorf(h), y1 = (int)ceilf(h);
               const float dx = w - (float)x0, dy = h - (float)y0;
-              const float u00 = dld<T>(pc + (long)y0 * g.ds_h + (long)x0 * g.ds_w), u01 = dld<T>(pc + (long)y1 * g.ds_h + (long)x0 * g.ds_w);
-              const float u10 = dld<T>(pc + (long)y0 * g.ds_h + (long)x1 * g.ds_w), u11 = dld<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
+              const float u00 = ldf<T>(pc + (long)y0 * g.ds_h + (long)x0 * g.ds_w), u01 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x0 * g.ds_w);
+              const float u10 = ldf<T>(pc + (long)y0 * g.ds_h + (long)x1 * g.ds_w), u11 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
               dtx += (u11 * dy + u10 * (1.f - dy) - u01 * dy - u00 * (1.f - dy)) * g.trans_std * diff * q.roi_w;
               dty += (u11 * dx + u01 * (1.f - dx) - u10 * dx - u00 * (1.f - dx)) * g.trans_std * diff * q.roi_h;
             }
@@ -811,7 +802,7 @@ __global__ __launch_bounds__(256) void deformable_psroi_pool_bwd_kernel(PsroiBwd
       ax.build(wstart, q.sub_w, g.spp, (float)g.W);
       ay.build(hstart, q.sub_h, g.spp, (float)g.H);
       const int count = ax.valid * ay.valid;                  // the forward's top_count
-      const float diff = count > 0 ? dld<T>(gop) / (float)count : 0.f;
+      const float diff = count > 0 ? ldf<T>(gop) / (float)count : 0.f;
       if (count > 0) {
 #pragma unroll
         for (int ky = 0; ky < 8; ++ky) {
@@ -837,8 +828,8 @@ __global__ __launch_bounds__(256) void deformable_psroi_pool_bwd_kernel(PsroiBwd
               h = fminf(fmaxf(h, 0.f), (float)g.H - 1.f);
               const int x0 = (int)floorf(w), x1 = (int)ceilf(w), y0 = (int)floorf(h), y1 = (int)ceilf(h);
               const float dx = w - (float)x0, dy = h - (float)y0;
-              const float u00 = dld<T>(pc + (long)y0 * g.ds_h + (long)x0 * g.ds_w), u01 = dld<T>(pc + (long)y1 * g.ds_h + (long)x0 * g.ds_w);
-              const float u10 = dld<T>(pc + (long)y0 * g.ds_h + (long)x1 * g.ds_w), u11 = dld<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
+              const float u00 = ldf<T>(pc + (long)y0 * g.ds_h + (long)x0 * g.ds_w), u01 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x0 * g.ds_w);
+              const float u10 = ldf<T>(pc + (long)y0 * g.ds_h + (long)x1 * g.ds_w), u11 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
               dtx += (u11 * dy + u10 * (1.f - dy) - u01 * dy - u00 * (1.f - dy)) * g.trans_std * diff * q.roi_w;
               dty += (u11 * dx + u01 * (1.f - dx) - u10 * dx - u00 * (1.f - dx)) * g.trans_std * diff * q.roi_h;
             }
@@ -867,7 +858,7 @@ __global__ __launch_bounds__(256) void deformable_psroi_pool_bwd_kernel(PsroiBwd
         if (!(w < -0.5f || w > (float)g.W - 0.5f || h < -0.5f || h > (float)g.H - 0.5f)) ++count;
       }
     if (count == 0) continue;
-    const float diff = dld<T>(gop) / (float)count;
+    const float diff = ldf<T>(gop) / (float)count;
     float dtx = 0.f, dty = 0.f;
     for (int ih = 0; ih < g.spp; ++ih)
       for (int iw = 0; iw < g.spp; ++iw) {
@@ -882,8 +873,8 @@ __global__ __launch_bounds__(256) void deformable_psroi_pool_bwd_kernel(PsroiBwd
         atomicAdd(gd + (long)y0 * a.gs_h + (long)x1 * a.gs_w, dx * (1.f - dy) * diff);
         atomicAdd(gd + (long)y1 * a.gs_h + (long)x1 * a.gs_w, dx * dy * diff);
         if (a.grad_trans) {
-          const float u00 = dld<T>(pc + (long)y0 * g.ds_h + (long)x0 * g.ds_w), u01 = dld<T>(pc + (long)y1 * g.ds_h + (long)x0 * g.ds_w);
-          const float u10 = dld<T>(pc + (long)y0 * g.ds_h + (long)x1 * g.ds_w), u11 = dld<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
+          const float u00 = ldf<T>(pc + (long)y0 * g.ds_h + (long)x0 * g.ds_w), u01 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x0 * g.ds_w);
+          const float u10 = ldf<T>(pc + (long)y0 * g.ds_h + (long)x1 * g.ds_w), u11 = ldf<T>(pc + (long)y1 * g.ds_h + (long)x1 * g.ds_w);
           dtx += (u11 * dy + u10 * (1.f - dy) - u01 * dy - u00 * (1.f - dy)) * g.trans_std * diff * q.roi_w;
           dty += (u11 * dx + u01 * (1.f - dx) - u10 * dx - u00 * (1.f - dx)) * g.trans_std * diff * q.roi_h;
         }

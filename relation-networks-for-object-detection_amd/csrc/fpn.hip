@@ -16,8 +16,6 @@
 
 namespace relnet {
 
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
-
 struct DispatchArgs {
   const float* rois; int box_stride, box_off;      // [B, N, box_stride], xyxy at box_off
   float* rois_out;                                  // [B, n_out, 5] level-sorted, column 0 = image index + base

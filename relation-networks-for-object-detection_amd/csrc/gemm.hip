@@ -45,13 +45,6 @@ struct GemmArgs {
   unsigned int* kcnt;
 };
 
-template <typename TOUT> __device__ __forceinline__ void store_out(TOUT* p, float v);
-template <> __device__ __forceinline__ void store_out<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void store_out<unsigned short>(unsigned short* p, float v) { *p = f2bf(v); }
-template <typename TOUT> __device__ __forceinline__ float load_out(const TOUT* p);
-template <> __device__ __forceinline__ float load_out<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float load_out<unsigned short>(const unsigned short* p) { return bf2f(*p); }
-
 // The residual operand of an epilogue: relu == 2 turns it into a ReLU MASK (backward of a fused conv + ReLU: the data gradient
 // is zeroed where the saved forward activation is not positive) instead of a summand.
 __device__ __forceinline__ float res_apply(float v, float r, int relu) { return relu == 2 ? (r > 0.f ? v : 0.f) : v + r; }
@@ -68,9 +61,9 @@ __device__ __forceinline__ void epilogue_tile(const GemmArgs& g, TOUT* C, const 
     if (row < g.M) {
       float v = acc[r] + bcol;
       if (g.bias_mode == 2) v += g.bias[row];
-      if (R) v = res_apply(v, load_out<TOUT>(R + (long)row * g.ldc + col), g.relu);
+      if (R) v = res_apply(v, ldf<TOUT>(R + (long)row * g.ldc + col), g.relu);
       if (g.relu == 1) v = fmaxf(v, 0.f);
-      store_out<TOUT>(C + (long)row * g.ldc + col, v);
+      stf<TOUT>(C + (long)row * g.ldc + col, v);
     }
   }
 }
@@ -121,9 +114,9 @@ __device__ __forceinline__ void epilogue_tile_t(const GemmArgs& g, TOUT* C, cons
         if (n + e < g.N) {
           float x = v[e];
           if (g.bias_mode == 1) x += g.bias[n + e];
-          if (rp) x = res_apply(x, load_out<TOUT>(rp + e), g.relu);
+          if (rp) x = res_apply(x, ldf<TOUT>(rp + e), g.relu);
           if (g.relu == 1) x = fmaxf(x, 0.f);
-          store_out<TOUT>(cp + e, x);
+          stf<TOUT>(cp + e, x);
         }
       }
     }
@@ -436,9 +429,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_bf16_kernel(GemmArgs g) 
         for (int e = 0; e < VEC; ++e) {
           if (n + e < g.N) {
             float x = v[e];
-            if (rp) x = res_apply(x, load_out<TOUT>(rp + e), g.relu);
+            if (rp) x = res_apply(x, ldf<TOUT>(rp + e), g.relu);
             if (g.relu == 1) x = fmaxf(x, 0.f);
-            store_out<TOUT>(cp + e, x);
+            stf<TOUT>(cp + e, x);
           }
         }
       }
@@ -488,9 +481,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_bf16_kernel(GemmArgs g) 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float x = v[e] + brow + (g.bias_mode == 1 ? g.bias[nn + e] : 0.f);
-        if (rp) x = res_apply(x, load_out<TOUT>(rp + e), g.relu);
+        if (rp) x = res_apply(x, ldf<TOUT>(rp + e), g.relu);
         if (g.relu == 1) x = fmaxf(x, 0.f);
-        if constexpr (MASK) x = load_out<TOUT>((const TOUT*)g.mask + (long)m * g.ldc + nn + e) > 0.f ? x : 0.f;
+        if constexpr (MASK) x = ldf<TOUT>((const TOUT*)g.mask + (long)m * g.ldc + nn + e) > 0.f ? x : 0.f;
         v[e] = x;
       }
       if constexpr (sizeof(TOUT) == 2) *(uint2*)cp = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
@@ -1463,9 +1456,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_ring_kernel(GemmArgs g) {
               for (int e = 0; e < 8; ++e) {
                 if (c + e < g.N) {
                   float x = v[e] + brow + (g.bias_mode == 1 ? g.bias[c + e] : 0.f);
-                  if (rp) x = res_apply(x, load_out<TOUT>(rp + e), g.relu);
+                  if (rp) x = res_apply(x, ldf<TOUT>(rp + e), g.relu);
                   if (g.relu == 1) x = fmaxf(x, 0.f);
-                  store_out<TOUT>(cp + e, x);
+                  stf<TOUT>(cp + e, x);
                 }
               }
             }
@@ -1492,9 +1485,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_ring_kernel(GemmArgs g) {
               for (int e = 0; e < 4; ++e) {
                 if (c + e < g.N) {
                   float x = v[e] + (g.bias_mode == 1 ? g.bias[c + e] : 0.f);
-                  if (rp) x = res_apply(x, load_out<TOUT>(rp + e), g.relu);
+                  if (rp) x = res_apply(x, ldf<TOUT>(rp + e), g.relu);
                   if (g.relu == 1) x = fmaxf(x, 0.f);
-                  store_out<TOUT>(cp + e, x);
+                  stf<TOUT>(cp + e, x);
                 }
               }
             }
@@ -1575,9 +1568,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_ring_kernel(GemmArgs g) {
         for (int e = 0; e < VEC; ++e) {
           if (n + e < g.N) {
             float x = v[e];
-            if (rp) x = res_apply(x, load_out<TOUT>(rp + e), g.relu);
+            if (rp) x = res_apply(x, ldf<TOUT>(rp + e), g.relu);
             if (g.relu == 1) x = fmaxf(x, 0.f);
-            store_out<TOUT>(cp + e, x);
+            stf<TOUT>(cp + e, x);
           }
         }
       }
@@ -2070,9 +2063,6 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(GemmArgs g) {
 }  // namespace relnet
 
 using namespace relnet;
-
-// dtype codes shared by the whole C-ABI
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
 
 static int g_ablate = 0;         // measurement knob (ring tiles, conv mode, bf16 out, no shortcut): 1 = fill path only, 2 = LDS + MFMA only
 extern "C" void relnet_gemm_debug_ablate(int a) { g_ablate = a; }

@@ -15,6 +15,7 @@
 // same input gives the same bits on every run.  A non-finite element (exponent bits all ones) adds to the count and nothing to the sum;
 // denormals are finite.  Squares of float32 values are exact in double and cannot overflow it (|x| < 2^128 -> x^2 < 2^256).
 #include "common.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -38,28 +39,6 @@ static_assert(sizeof(GuardState) == 64, "relnet_grad_guard_state is 64 bytes");
 
 struct StatsRange { const float* p; long n; int blk_start, blocks; };
 struct StatsGroup { StatsRange r[kGuardMaxRanges]; int n; GuardSlot* slots; };
-
-__device__ __forceinline__ double guard_wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ long long guard_wave_sum(long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-// workgroup sum in wave order (one barrier; s holds kGuardWaves values and belongs to this call alone); valid in thread 0
-template <typename V>
-__device__ __forceinline__ V guard_block_sum(V v, V* s) {
-  v = guard_wave_sum(v);
-  if ((threadIdx.x & (kWave - 1)) == 0) s[threadIdx.x / kWave] = v;
-  __syncthreads();
-  V t = s[0];
-#pragma unroll
-  for (int w = 1; w < kGuardWaves; ++w) t += s[w];
-  return t;
-}
 
 __device__ __forceinline__ void guard_one(float x, double& a, long long& c) {
   const bool bad = (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;      // inf or NaN
@@ -96,8 +75,8 @@ __global__ __launch_bounds__(kGuardThreads) void grad_stats_kernel(StatsGroup g)
     if ((long)threadIdx.x < head) guard_one(a.p[threadIdx.x], acc, cnt);
     if ((long)threadIdx.x < tail) guard_one(a.p[head + 4 * nvec + threadIdx.x], acc, cnt);
   }
-  const double bs = guard_block_sum(acc, s_d);
-  const long long bc = guard_block_sum(cnt, s_c);
+  const double bs = block_sum<kGuardWaves>(acc, s_d);
+  const long long bc = block_sum<kGuardWaves>(cnt, s_c);
   if (threadIdx.x == 0) {
     GuardSlot o;
     o.sumsq = bs; o.nonfinite = bc;
@@ -111,8 +90,8 @@ __global__ __launch_bounds__(kGuardThreads) void grad_guard_decide_kernel(const 
   double acc = 0.0;
   long long cnt = 0;
   for (long i = threadIdx.x; i < n_slots; i += kGuardThreads) { acc += slots[i].sumsq; cnt += slots[i].nonfinite; }
-  const double sumsq = guard_block_sum(acc, s_d);
-  const long long bad = guard_block_sum(cnt, s_c);
+  const double sumsq = block_sum<kGuardWaves>(acc, s_d);
+  const long long bad = block_sum<kGuardWaves>(cnt, s_c);
   if (threadIdx.x != 0) return;
   const double norm = sqrt(sumsq);
   GuardState s = *st;

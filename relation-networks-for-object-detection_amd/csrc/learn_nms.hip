@@ -15,6 +15,8 @@
 // (image, class) pairs as the batch dimension and the 8-wide per-head value padded to the 64-wide
 // tile (zero rows in the packed linear_out weight).
 #include "common.h"
+#include "ordering.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -31,19 +33,6 @@ struct PrepArgs {
 };
 
 #pragma clang fp contract(off)
-// One wavefront: prob[c - 1] = softmax(z)[c] for the foreground classes c = 1..C-1.
-__device__ __forceinline__ void softmax_row_fg(const float* z, float* prob, int C, int lane) {
-  float m = -INFINITY;
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += expf(z[c] - m);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  for (int c = lane + 1; c < C; c += 64) prob[c - 1] = expf(z[c] - m) / s;
-}
-
 // refine_bbox_nd (learn_nms.py:175-217) of ONE box in float32: roi [5], d = its four deltas, info = the image's (h, w, scale).
 __device__ __forceinline__ float4 refine_box(const PrepArgs& g, const float* roi, const float* d, const float* info) {
   const float x1 = roi[1], y1 = roi[2], x2 = roi[3], y2 = roi[4];
@@ -67,7 +56,7 @@ __global__ __launch_bounds__(64) void lnms_prepare_kernel(PrepArgs g) {
     if (lane == 0) *(float4*)(g.boxes + (long)r * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
-  softmax_row_fg(g.cls_score + (long)r * g.cs_ld, g.prob + (long)r * (g.C - 1), g.C, lane);
+  softmax_row(g.cls_score + (long)r * g.cs_ld, g.prob + (long)r * (g.C - 1), g.C, lane, 1);
   if (lane == 0)
     *(float4*)(g.boxes + (long)r * 4) = refine_box(g, g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + g.delta_off,
                                                    g.im_info + (long)(r / g.N) * 3);
@@ -85,17 +74,12 @@ __global__ __launch_bounds__(64) void lnms_prepare_cs_kernel(PrepArgs g) {
     }
     return;
   }
-  softmax_row_fg(g.cls_score + (long)r * g.cs_ld, g.prob + (long)r * NC, g.C, lane);
+  softmax_row(g.cls_score + (long)r * g.cs_ld, g.prob + (long)r * NC, g.C, lane, 1);
   for (int k = lane; k < NC; k += 64)
     *(float4*)(out + 4 * k) = refine_box(g, g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + 4 * (k + 1),
                                          g.im_info + (long)(r / g.N) * 3);
 }
 #pragma clang fp contract(fast)
-
-__device__ __forceinline__ unsigned int fkey32(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct SortArgs {
   const float* prob;      // [B, N, NC]
@@ -117,22 +101,11 @@ __global__ __launch_bounds__(256) void lnms_sort_kernel(SortArgs g) {
   while (np2 < g.N) np2 <<= 1;
   for (int i = tid; i < np2; i += 256) {
     unsigned long long k = 0ull;
-    if (i < g.N) k = ((unsigned long long)fkey32(g.prob[((long)b * g.N + i) * g.NC + c]) << 16) | (unsigned)(0xffff - i);
+    if (i < g.N) k = ((unsigned long long)order_key(g.prob[((long)b * g.N + i) * g.NC + c]) << 16) | (unsigned)(0xffff - i);
     keys[i] = k;
   }
   __syncthreads();
-  for (int k = 2; k <= np2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < np2; i += 256) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], d = keys[ixj];
-          const bool desc = (i & k) == 0;
-          if (desc ? (a < d) : (a > d)) { keys[i] = d; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_desc<256>(keys, np2);
   for (int r = tid; r < g.F; r += 256) {
     const int idx = 0xffff - (int)(keys[r] & 0xffffu);
     const float s = g.prob[((long)b * g.N + idx) * g.NC + c];
@@ -203,8 +176,7 @@ __global__ __launch_bounds__(64) void lnms_score_kernel(ScoreArgs g) {
   // valid-class rule (learn_nms.py:293-302): max score of the class >= min(class_thresh, global max)
   float gm = -INFINITY;
   for (int k = lane; k < g.NC; k += 64) gm = fmaxf(gm, g.class_max[(long)b * g.NC + k]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gm = fmaxf(gm, __shfl_xor(gm, o));
+  gm = wave_max(gm);
   const bool valid = g.class_max[(long)b * g.NC + c] >= fminf(g.class_thresh, gm);
   cfloat_p wl = (cfloat_p)(unsigned long long)g.w_logit;
   cfloat_p bl = (cfloat_p)(unsigned long long)g.b_logit;

@@ -10,6 +10,7 @@
 //   relnet_lnms_softmax_bwd    adjoint of softmax + slice_axis(begin=1) (:430-433), accumulated into the detector's d cls_score
 //   relnet_lnms_gather_bias    the per-(image, class) geometry bias gathered from one per-image table by the class's ranks
 #include "common.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -180,8 +181,7 @@ __global__ __launch_bounds__(256) void lnms_softmax_bwd_kernel(const float* prob
   const float* dp = d_prob + row * C;
   float sp = 0.f, si = 0.f;
   for (int c = lane; c < C; c += 64) { const float p = pp[c]; sp += p; si += p * dp[c]; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); si += __shfl_xor(si, o, 64); }
+  sp = wave_sum(sp); si = wave_sum(si);
   float* out = d_cls + b * ld_img + n * ld_row;
   if (lane == 0) out[0] += -(1.f - sp) * si;
   for (int c = lane; c < C; c += 64) out[1 + c] += pp[c] * (dp[c] - si);

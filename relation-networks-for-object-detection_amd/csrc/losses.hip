@@ -13,6 +13,7 @@
 //                            with k = nms_loss_scale / (first_n * num_thresh); MakeLoss grad_scale = nms_pos_scale on
 //                            the positive term.
 #include "common.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -39,8 +40,7 @@ __global__ __launch_bounds__(256) void softmax_count_kernel(SoftmaxOutArgs g) {
     const long grp = (in ? idx : total - 1) / g.group;
     const long g0 = __shfl(grp, 0);
     if (__all(grp == g0)) {                       // the usual case: one normalisation group per wavefront -> one atomic
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
+      local = wave_sum(local);
       if ((threadIdx.x & 63) == 0 && local) atomicAdd(g.valid_count + g0, local);
     } else if (local) {
       atomicAdd(g.valid_count + grp, 1);

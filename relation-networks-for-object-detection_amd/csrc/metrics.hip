@@ -11,6 +11,7 @@
 // counter, so a workspace is zeroed once, when it is created.  Launches that share a workspace must be ordered by their stream
 // (the trainers keep one workspace per branch: RPN metrics on the side stream, the others on the main stream).
 #include "common.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -30,30 +31,6 @@ __device__ __forceinline__ MetricWorkspace metric_ws(void* p) {
   w.counter = (unsigned int*)p;
   w.slab = (unsigned long long*)((char*)p + 64);
   return w;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// Workgroup sum in wave order, returned to every thread.  Contains one barrier; s holds kMetricWaves values and belongs to this
-// call alone (each sum of a kernel has its own array).
-template <typename V>
-__device__ __forceinline__ V block_sum(V v, V* s) {
-  v = wave_sum(v);
-  if ((threadIdx.x & (kWave - 1)) == 0) s[threadIdx.x / kWave] = v;
-  __syncthreads();
-  V t = s[0];
-#pragma unroll
-  for (int w = 1; w < kMetricWaves; ++w) t += s[w];
-  return t;
 }
 
 // Deterministic cross-workgroup fold of up to kMetricSlabs double partials per workgroup (thread 0 holds them).  Every
@@ -165,8 +142,8 @@ __global__ __launch_bounds__(kMetricThreads) void metric_softmax_inner_kernel(So
       loss += log_loss_term(pl);                         // (a label outside [0, C) reads nothing: p = 0)
     }
   }
-  const long long bc = block_sum(correct, s_c), bi = block_sum(inst, s_i);
-  const double part[1] = {block_sum(loss, s_d)};
+  const long long bc = block_sum<kMetricWaves>(correct, s_c), bi = block_sum<kMetricWaves>(inst, s_i);
+  const double part[1] = {block_sum<kMetricWaves>(loss, s_d)};
   if (threadIdx.x == 0) {
     if (bc) atomicAdd((unsigned long long*)g.correct, (unsigned long long)bc);
     if (bi) atomicAdd((unsigned long long*)g.inst, (unsigned long long)bi);
@@ -206,8 +183,8 @@ __global__ __launch_bounds__(kMetricThreads) void metric_softmax_row_kernel(Soft
       loss += log_loss_term(lab >= 0 && lab < g.C ? row[lab] : 0.f);
     }
   }
-  const long long bc = block_sum(correct, s_c), bi = block_sum(inst, s_i);
-  const double part[1] = {block_sum(loss, s_d)};
+  const long long bc = block_sum<kMetricWaves>(correct, s_c), bi = block_sum<kMetricWaves>(inst, s_i);
+  const double part[1] = {block_sum<kMetricWaves>(loss, s_d)};
   if (threadIdx.x == 0) {
     if (bc) atomicAdd((unsigned long long*)g.correct, (unsigned long long)bc);
     if (bi) atomicAdd((unsigned long long*)g.inst, (unsigned long long)bi);
@@ -268,8 +245,8 @@ __global__ __launch_bounds__(kMetricThreads) void metric_sum_count_kernel(SumCou
     for (long t = g.n_label / 4 * 4; t < g.n_label; ++t) cnt += g.label[t] != -1.f;
   }
   if (first == 0) cnt += g.inst_inc;
-  const long long bc = block_sum(cnt, s_c);
-  const double part[2] = {block_sum(a, s_d), block_sum(a2, s_d2)};
+  const long long bc = block_sum<kMetricWaves>(cnt, s_c);
+  const double part[2] = {block_sum<kMetricWaves>(a, s_d), block_sum<kMetricWaves>(a2, s_d2)};
   if (threadIdx.x == 0 && bc && g.count) atomicAdd((unsigned long long*)g.count, (unsigned long long)bc);
   double* const slot[2] = {g.sum, g.x2 ? g.sum2 : nullptr};
   fold_and_add<2>(metric_ws(g.ws), part, slot, s_fold, &s_flag);

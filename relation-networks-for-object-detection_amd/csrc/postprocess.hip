@@ -11,6 +11,8 @@
 //                           greedy NMS (drop iou > thresh); all arithmetic float64 like numpy.
 //   image_topk_kernel       image-level score threshold = max_per_image-th largest score.
 #include "common.h"
+#include "ordering.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -26,19 +28,6 @@ struct HeadArgs {
 };
 
 #pragma clang fp contract(off)
-// One wavefront: cls_prob[c] = softmax(z)[c] over C classes.
-__device__ __forceinline__ void softmax_row(const float* z, float* prob, int C, int lane) {
-  float m = -INFINITY;
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += expf(z[c] - m);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  for (int c = lane; c < C; c += 64) prob[c] = expf(z[c] - m) / s;
-}
-
 // bbox_pred (bbox_transform.py:103-140, float64 on float32 deltas, exp rounded to float32 like numpy) + clip_boxes + 1 / scale
 // of ONE box: roi [5], d = its four deltas, info = the image's (h, w, scale).
 __device__ __forceinline__ void decode_box(const float* roi, const float* d, const float* info, double o[4]) {
@@ -62,7 +51,7 @@ __global__ __launch_bounds__(64) void detect_head_kernel(HeadArgs g) {
     if (lane < 4) g.boxes[(long)r * 4 + lane] = 0.0;
     return;
   }
-  softmax_row(g.cls_score + (long)r * g.cs_ld, g.cls_prob + (long)r * g.C, g.C, lane);
+  softmax_row(g.cls_score + (long)r * g.cs_ld, g.cls_prob + (long)r * g.C, g.C, lane, 0);
   if (lane == 0) {
     double o[4];
     decode_box(g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + g.delta_off, g.im_info + (long)(r / g.rois_per_image) * 3, o);
@@ -81,7 +70,7 @@ __global__ __launch_bounds__(64) void detect_head_cs_kernel(HeadArgs g) {
     for (int k = lane; k < 4 * g.C; k += 64) out[k] = 0.0;
     return;
   }
-  softmax_row(g.cls_score + (long)r * g.cs_ld, g.cls_prob + (long)r * g.C, g.C, lane);
+  softmax_row(g.cls_score + (long)r * g.cs_ld, g.cls_prob + (long)r * g.C, g.C, lane, 0);
   for (int c = lane; c < g.C; c += 64) {
     double o[4];
     decode_box(g.rois + (long)r * 5, g.bbox_pred + (long)r * g.bp_ld + 4 * c, g.im_info + (long)(r / g.rois_per_image) * 3, o);
@@ -138,37 +127,6 @@ __device__ __forceinline__ int score_bin(double sc, int& fine) {
 // "absent / already picked / suppressed" marker of a candidate's score.  -inf, not -1: the lib/nms/nms.py twins accept any
 // float64 dets[:, 4] (raw logits, negative scores), which must stay distinguishable from removed slots.
 #define kGone (-INFINITY)
-
-// Wave-wide maximum of a double without LDS traffic: four DPP steps inside each row of 16 lanes (quad_perm xor 1 / xor 2,
-// row_half_mirror, row_mirror: the maximum is idempotent, mirrored partners are as good as a butterfly), then the four row values
-// through v_readlane.  (__shfl_xor of a double is two ds_bpermute round trips per step; the per-pick arg-max chain of the
-// class-NMS kernels is latency bound.)  The result is the same in every lane.
-template <int CTRL> __device__ __forceinline__ double dpp_move_f64(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-  v = fmax(v, dpp_move_f64<0xB1>(v));        // quad_perm [1,0,3,2]
-  v = fmax(v, dpp_move_f64<0x4E>(v));        // quad_perm [2,3,0,1]
-  v = fmax(v, dpp_move_f64<0x141>(v));       // row_half_mirror
-  v = fmax(v, dpp_move_f64<0x140>(v));       // row_mirror
-  return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
-}
-
-// Wave-wide sum of an unsigned (same DPP pairing as wave_max_f64: every step adds two disjoint groups).
-__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
-  v += (unsigned int)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, false);
-  v += (unsigned int)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, false);
-  v += (unsigned int)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xf, 0xf, false);
-  v += (unsigned int)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xf, 0xf, false);
-  return (unsigned int)__builtin_amdgcn_readlane((int)v, 0) + (unsigned int)__builtin_amdgcn_readlane((int)v, 16) +
-         (unsigned int)__builtin_amdgcn_readlane((int)v, 32) + (unsigned int)__builtin_amdgcn_readlane((int)v, 48);
-}
 
 // One workgroup of WAVES wavefronts per (image, class), PER candidates per thread (candidate s of thread t = roi s * 64 WAVES + t).
 // The per-pick chain is the serial path of the whole post-processing (a class that owns k of the image's max_per_image
@@ -231,7 +189,7 @@ __global__ __launch_bounds__(64 * WAVES) void class_nms_kernel(ClsNmsArgs g) {
     double lbest = sc[0];
 #pragma unroll
     for (int s = 1; s < PER; ++s) lbest = fmax(lbest, sc[s]);
-    double best = wave_max_f64(lbest);
+    double best = wave_max_dpp(lbest);
     int bi = -1;
 #pragma unroll
     for (int s = PER - 1; s >= 0; --s) {
@@ -252,7 +210,7 @@ __global__ __launch_bounds__(64 * WAVES) void class_nms_kernel(ClsNmsArgs g) {
         unsigned int part = (lane < kHistFine && lane > myfine) ? hf : 0u;
 #pragma unroll
         for (int q = 0; q < 6; ++q) part += (lane * 6 + q > mybin) ? hc[q] : 0u;
-        stop = wave_sum_u32(part) >= (unsigned int)g.top_k;
+        stop = wave_sum_dpp(part) >= (unsigned int)g.top_k;
       }
     }
     if constexpr (WAVES > 1) {
@@ -324,11 +282,6 @@ struct ImgTopkArgs {
   int NC, N, max_per_image, max_out;
 };
 
-__device__ __forceinline__ unsigned long long dkey(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 constexpr int kTopkKeys = 6144;          // pick keys cached in LDS (48 KB); longer lists are re-read from global memory every pass
 
 // One workgroup per image.  The picks of the image's classes are ONE list of `total` entries (class-major, pick order = the order
@@ -367,7 +320,7 @@ __global__ __launch_bounds__(1024) void image_topk_kernel(ImgTopkArgs g) {
     for (int i = tid; i < total; i += 1024) {
       const int c = class_of(i);
       s_cls[i] = (unsigned char)c;
-      s_keys[i] = dkey(dets[((long)c * g.N + (i - s_off[c])) * 5 + 4]);
+      s_keys[i] = order_key(dets[((long)c * g.N + (i - s_off[c])) * 5 + 4]);
     }
     if (tid == 0) { s_prefix = 0ull; s_remaining = g.max_per_image; }
     __syncthreads();
@@ -442,7 +395,7 @@ __global__ __launch_bounds__(1024) void image_topk_kernel(ImgTopkArgs g) {
   // ---- general path: the keys are re-read from global memory in every pass
   auto key_of = [&](int i) {
     const int c = class_of(i);
-    return dkey(dets[((long)c * g.N + (i - s_off[c])) * 5 + 4]);
+    return order_key(dets[((long)c * g.N + (i - s_off[c])) * 5 + 4]);
   };
   unsigned long long kth = 0ull;
   if (total > g.max_per_image) {
@@ -481,7 +434,7 @@ __global__ __launch_bounds__(1024) void image_topk_kernel(ImgTopkArgs g) {
   // per-class kept counts -> offsets
   for (int c = tid; c < g.NC; c += 1024) {
     int kc = 0;
-    for (int k = 0; k < cnt[c]; ++k) kc += (dkey(dets[((long)c * g.N + k) * 5 + 4]) >= kth) ? 1 : 0;
+    for (int k = 0; k < cnt[c]; ++k) kc += (order_key(dets[((long)c * g.N + k) * 5 + 4]) >= kth) ? 1 : 0;
     s_off[c] = kc;
   }
   __syncthreads();
@@ -495,7 +448,7 @@ __global__ __launch_bounds__(1024) void image_topk_kernel(ImgTopkArgs g) {
     int pos = s_off[c];
     for (int k = 0; k < cnt[c]; ++k) {
       const double* d = dets + ((long)c * g.N + k) * 5;
-      if (dkey(d[4]) >= kth) {
+      if (order_key(d[4]) >= kth) {
         if (pos < g.max_out) {
           float* o = g.out + ((long)b * g.max_out + pos) * 6;
           o[0] = (float)(c + 1); o[1] = (float)d[4]; o[2] = (float)d[0]; o[3] = (float)d[1]; o[4] = (float)d[2]; o[5] = (float)d[3];

@@ -13,6 +13,8 @@
 // Tie rule (the reference's unstable argsort leaves it open): equal scores are ordered by
 // descending original index, i.e. `argsort(kind='stable')[::-1]`.
 #include "common.h"
+#include "ordering.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -65,14 +67,8 @@ __global__ __launch_bounds__(256) void proposal_decode_kernel(DecodeArgs g) {
   g.scores[(long)b * n + idx] = ok ? score : -INFINITY;
 }
 
-// order-preserving float -> uint32 (larger float => larger key); -inf smallest finite-ish
-__device__ __forceinline__ unsigned int fkey(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // ---------------------------------------------------------------------------------------
-// top-K + sort.  Composite key = (fkey(score) << 16) | idx  (idx < 65536), descending.
+// top-K + sort.  Composite key = (order_key(score) << 16) | idx  (idx < 65536), descending.
 // ---------------------------------------------------------------------------------------
 constexpr int kSortCap = 8192;       // LDS bitonic capacity (64 KiB of uint64)
 constexpr int kSortThreads = 1024;
@@ -107,9 +103,9 @@ __global__ __launch_bounds__(kSortThreads) void topk_sort_kernel(TopkArgs g) {
 #pragma unroll
   for (int s = 0; s < PER; ++s) {
     const int i = s * kSortThreads + tid;
-    fk[s] = i < g.n ? fkey(sc[i]) : 0u;
+    fk[s] = i < g.n ? order_key(sc[i]) : 0u;
   }
-  // ---- radix select: find the K-th largest composite key (fkey << 16 | index) --------------------
+  // ---- radix select: find the K-th largest composite key (order_key << 16 | index) --------------------
   if (tid == 0) { s_prefix = 0ull; s_remaining = K; s_count = 0; s_valid = 0; }
   for (int i = tid; i < kSortCap; i += kSortThreads) keys[i] = 0ull;
   __syncthreads();
@@ -172,17 +168,7 @@ __global__ __launch_bounds__(kSortThreads) void topk_sort_kernel(TopkArgs g) {
   // ---- bitonic sort, descending, over the next power of two >= K: thread = pair (i, i | j) ---------------------
   int np2 = 1;
   while (np2 < K) np2 <<= 1;
-  for (int k = 2; k <= np2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int p = tid; p < (np2 >> 1); p += kSortThreads) {
-        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), ixj = i | j;
-        const unsigned long long a = keys[i], c = keys[ixj];
-        const bool desc = (i & k) == 0;
-        if (desc ? (a < c) : (a > c)) { keys[i] = c; keys[ixj] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_sort_desc_pairs<kSortThreads>(keys, np2);
   // ---- gather ------------------------------------------------------------------------
   int valid = 0;
   for (int i = tid; i < K; i += kSortThreads) {
@@ -196,8 +182,7 @@ __global__ __launch_bounds__(kSortThreads) void topk_sort_kernel(TopkArgs g) {
     valid += (s > -INFINITY) ? 1 : 0;
   }
   // count of finite-score entries (filtered boxes carry -inf and sort last)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) valid += __shfl_xor(valid, o);
+  valid = wave_sum(valid);
   if (lane == 0 && valid) atomicAdd(&s_valid, valid);
   __syncthreads();
   if (tid == 0) g.out_count[b] = s_valid;

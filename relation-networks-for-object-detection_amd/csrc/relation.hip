@@ -14,6 +14,7 @@
 //                         with d_k = d_v = 64 (executed FLOPs 4.4x below the graph as
 //                         written; DESIGN.md reports both).
 #include "common.h"
+#include "relation_geom.h"
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
@@ -38,21 +39,6 @@ struct GeomArgs {
 };
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ void position_features(float4 bi, float4 bj, float (&p)[4]) {
-  // bit-for-bit the fp32 op sequence of SYM_REL:59-77; log is correctly rounded (fp64
-  // evaluation) because a 1-ulp log difference is amplified x100 before sin/cos.
-  const float wi = bi.z - bi.x + 1.f, hi = bi.w - bi.y + 1.f;
-  const float wj = bj.z - bj.x + 1.f, hj = bj.w - bj.y + 1.f;
-  const float cxi = 0.5f * (bi.x + bi.z), cyi = 0.5f * (bi.y + bi.w);
-  const float cxj = 0.5f * (bj.x + bj.z), cyj = 0.5f * (bj.y + bj.w);
-  const float dx = fmaxf(fabsf((cxi - cxj) / wi), 1e-3f);
-  const float dy = fmaxf(fabsf((cyi - cyj) / hi), 1e-3f);
-  p[0] = (float)log((double)dx);
-  p[1] = (float)log((double)dy);
-  p[2] = (float)log((double)(wi / wj));
-  p[3] = (float)log((double)(hi / hj));
-}
-
 // EXACT (float output only): the float32 PARITY form -- sin / cos / log correctly rounded (float64 evaluation, one rounding)
 // and the 64 -> 16 pair_pos_fc1 product accumulated in float64 and rounded once, i.e. the arithmetic of oracle/relation.py
 // (`cr`, `_mm`): the logits `weighted_aff` (SYM_REL:139) then agree with the oracle to float32 rounding for EVERY pair,
@@ -940,7 +926,6 @@ __global__ __launch_bounds__(1024) void relation_fused_kernel(FusedArgs f) {
 }  // namespace relnet
 
 using namespace relnet;
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
 
 extern "C" int relnet_geometry_bias(const float* boxes, int box_stride, int box_off,
                                     const float* wp, const float* bp, const float* divisors8,

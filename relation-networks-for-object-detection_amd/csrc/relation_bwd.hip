@@ -20,10 +20,9 @@
 //        per lane), dpre comes from dL and the forward's log G, dWp accumulates in a 32x32x2 fp32 MFMA tile.
 //  transpose_2d_kernel               [rows][cols] -> [cols][rows] through an LDS tile (operand layouts above).
 #include "common.h"
+#include "relation_geom.h"
 
 namespace relnet {
-
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
 
 // ---------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -613,32 +612,6 @@ struct GeomBwdArgs {
 constexpr int kGeomPartWords = 16 * 64 + 16;      // one slot: dwp [16][64], then dbp [16]
 
 #pragma clang fp contract(off)
-__device__ __forceinline__ float position_feature_1(float4 bi, float4 bj, int comp) {
-  // relation.hip:position_features, one component
-  const float wi = bi.z - bi.x + 1.f, hi = bi.w - bi.y + 1.f;
-  const float wj = bj.z - bj.x + 1.f, hj = bj.w - bj.y + 1.f;
-  const float cxi = 0.5f * (bi.x + bi.z), cyi = 0.5f * (bi.y + bi.w);
-  const float cxj = 0.5f * (bj.x + bj.z), cyj = 0.5f * (bj.y + bj.w);
-  float v;
-  if (comp == 0) v = fmaxf(fabsf((cxi - cxj) / wi), 1e-3f);
-  else if (comp == 1) v = fmaxf(fabsf((cyi - cyj) / hi), 1e-3f);
-  else if (comp == 2) v = wi / wj;
-  else v = hi / hj;
-  return (float)log((double)v);
-}
-__device__ __forceinline__ void position_features(float4 bi, float4 bj, float (&p)[4]) {
-  // identical to relation.hip:position_features (bit-exact fp32 sequence of SYM_REL:59-77, correctly rounded logs)
-  const float wi = bi.z - bi.x + 1.f, hi = bi.w - bi.y + 1.f;
-  const float wj = bj.z - bj.x + 1.f, hj = bj.w - bj.y + 1.f;
-  const float cxi = 0.5f * (bi.x + bi.z), cyi = 0.5f * (bi.y + bi.w);
-  const float cxj = 0.5f * (bj.x + bj.z), cyj = 0.5f * (bj.y + bj.w);
-  const float dx = fmaxf(fabsf((cxi - cxj) / wi), 1e-3f);
-  const float dy = fmaxf(fabsf((cyi - cyj) / hi), 1e-3f);
-  p[0] = (float)log((double)dx);
-  p[1] = (float)log((double)dy);
-  p[2] = (float)log((double)(wi / wj));
-  p[3] = (float)log((double)(hi / hj));
-}
 template <bool FAST>
 __device__ __forceinline__ float embed_value(float p, int sc, float divisor) {
   const float arg = (100.0f * p) / divisor;

@@ -27,13 +27,6 @@ struct RoiAlignArgs {
   struct Level { const void* data; long ds_b, ds_c, ds_h, ds_w; float* grad; long gs_b, gs_c, gs_h, gs_w; int H, W; float scale; } lv[4];
 };
 
-template <typename T> __device__ __forceinline__ float ra_ld(const T* p);
-template <> __device__ __forceinline__ float ra_ld<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ra_ld<unsigned short>(const unsigned short* p) { return bf2f(*p); }
-template <typename T> __device__ __forceinline__ void ra_st(T* p, float v);
-template <> __device__ __forceinline__ void ra_st<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void ra_st<unsigned short>(unsigned short* p, float v) { *p = f2bf(v); }
-
 #pragma clang fp contract(off)
 struct RoiBin { int b; float start_h, start_w, bin_h, bin_w; int grid_h, grid_w; float count; };
 
@@ -93,7 +86,7 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(RoiAlignArgs g) {
   const RoiAlignMap m = roi_align_map(g, r);
   T* out = (T*)g.out + (long)r * g.os_r + (long)ph * g.os_ph + (long)pw * g.os_pw;
   if (!m.ok) {
-    for (int c = threadIdx.x; c < g.C; c += 256) ra_st<T>(out + (long)c * g.os_c, 0.f);
+    for (int c = threadIdx.x; c < g.C; c += 256) stf<T>(out + (long)c * g.os_c, 0.f);
     return;
   }
   const RoiBin q = roi_bin(g, r, m.scale);
@@ -107,12 +100,12 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(RoiAlignArgs g) {
         const float x = q.start_w + (float)pw * q.bin_w + ((float)ix + 0.5f) * q.bin_w / (float)q.grid_w;
         Corners k;
         if (!corners(y, x, m.H, m.W, k)) continue;
-        const float v1 = ra_ld<T>(pc + (long)k.yl * m.ds_h + (long)k.xl * m.ds_w), v2 = ra_ld<T>(pc + (long)k.yl * m.ds_h + (long)k.xh * m.ds_w);
-        const float v3 = ra_ld<T>(pc + (long)k.yh * m.ds_h + (long)k.xl * m.ds_w), v4 = ra_ld<T>(pc + (long)k.yh * m.ds_h + (long)k.xh * m.ds_w);
+        const float v1 = ldf<T>(pc + (long)k.yl * m.ds_h + (long)k.xl * m.ds_w), v2 = ldf<T>(pc + (long)k.yl * m.ds_h + (long)k.xh * m.ds_w);
+        const float v3 = ldf<T>(pc + (long)k.yh * m.ds_h + (long)k.xl * m.ds_w), v4 = ldf<T>(pc + (long)k.yh * m.ds_h + (long)k.xh * m.ds_w);
         sum += ((k.w1 * v1 + k.w2 * v2) + k.w3 * v3) + k.w4 * v4;
       }
     }
-    ra_st<T>(out + (long)c * g.os_c, sum / q.count);
+    stf<T>(out + (long)c * g.os_c, sum / q.count);
   }
 }
 
@@ -166,7 +159,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(RoiAlignArgs g) {
   const RoiBin q = roi_bin(g, r, g.scale);
   float* gb = g.grad_in + (long)q.b * g.gs_b;
   for (int c = threadIdx.x; c < g.C; c += 256) {
-    const float go = ra_ld<T>((const T*)g.out + (long)r * g.os_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw) / q.count;
+    const float go = ldf<T>((const T*)g.out + (long)r * g.os_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw) / q.count;
     float* gc = gb + (long)c * g.gs_c;
     for (int iy = 0; iy < q.grid_h; ++iy) {
       const float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
@@ -263,7 +256,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_levels_kernel(RoiAlignArgs 
         float go[PP * PP];
 #pragma unroll
         for (int i = 0; i < PP * PP; ++i)
-          go[i] = ra_ld<T>(go_r + (long)c * g.os_c + (long)(i / PP) * g.os_ph + (long)(i % PP) * g.os_pw);
+          go[i] = ldf<T>(go_r + (long)c * g.os_c + (long)(i / PP) * g.os_ph + (long)(i % PP) * g.os_pw);
         float* gc = gb + (long)c * m.gs_c + (long)y0 * m.gs_h + (long)x0 * m.gs_w;
         for (int x = 0; x < FW; ++x) {
           float t[PP];                                     // (Go Wx)[:, x]
@@ -290,7 +283,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_levels_kernel(RoiAlignArgs 
     float* gc = gb + (long)c * m.gs_c;
     for (int ph = 0; ph < g.PH; ++ph)
       for (int pw = 0; pw < g.PW; ++pw) {
-        const float go = ra_ld<T>(go_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw) / q.count;
+        const float go = ldf<T>(go_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw) / q.count;
         for (int iy = 0; iy < q.grid_h; ++iy) {
           const float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
           for (int ix = 0; ix < q.grid_w; ++ix) {
@@ -311,7 +304,6 @@ __global__ __launch_bounds__(256) void roi_align_bwd_levels_kernel(RoiAlignArgs 
 }  // namespace relnet
 
 using namespace relnet;
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
 
 // the forward launch shared by both entries (g.lv / level / num_levels / B filled in)
 static int launch_roi_align_fwd(const RoiAlignArgs& g, const void* out, int dtype, void* stream, const char* what) {

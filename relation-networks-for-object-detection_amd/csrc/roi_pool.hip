@@ -37,13 +37,6 @@ __device__ __forceinline__ RoiMap roi_map(const RoiArgs& g, int r) {
   return m;
 }
 
-template <typename T> __device__ __forceinline__ float ld(const T* p);
-template <> __device__ __forceinline__ float ld<float>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float ld<unsigned short>(const unsigned short* p) { return bf2f(*p); }
-template <typename T> __device__ __forceinline__ void st(T* p, float v);
-template <> __device__ __forceinline__ void st<float>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void st<unsigned short>(unsigned short* p, float v) { *p = f2bf(v); }
-
 #pragma clang fp contract(off)
 // grid.x = R * PH * PW bins, threads stride over channels
 template <typename T>
@@ -69,11 +62,11 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(RoiArgs g) {
     const T* pc = base + (long)c * m.ds_c;
     for (int y = hs; y < he; ++y)
       for (int x = ws; x < we; ++x) {
-        const float v = ld<T>(pc + (long)y * m.ds_h + (long)x * m.ds_w);
+        const float v = ldf<T>(pc + (long)y * m.ds_h + (long)x * m.ds_w);
         if (v > best) { best = v; bi = y * m.W + x; }
       }
     const long o = (long)r * g.os_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw;
-    st<T>((T*)g.out + o, best);
+    stf<T>((T*)g.out + o, best);
     if (g.argmax) g.argmax[o] = bi;
   }
 }
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_kernel(RoiBwdArgs g) {
   for (int c = threadIdx.x; c < g.C; c += 256) {
     const long o = (long)r * g.os_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw;
     const int a = g.argmax[o];
-    if (a >= 0) atomicAdd(gin + (long)b * ds_b + (long)c * ds_c + (long)a * ds_p, ld<T>((const T*)g.grad_out + o));
+    if (a >= 0) atomicAdd(gin + (long)b * ds_b + (long)c * ds_c + (long)a * ds_p, ldf<T>((const T*)g.grad_out + o));
   }
 }
 
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_ordered_kernel(RoiBwdOrdArgs
             if (a[2 * e + 1] == cell) acc[2 * e + 1] += bf2f(w4[e] >> 16);
           }
         } else {
-          if (g.argmax[o] == cell) acc[0] += ld<T>((const T*)g.grad_out + o);
+          if (g.argmax[o] == cell) acc[0] += ldf<T>((const T*)g.grad_out + o);
         }
       }
     }
@@ -240,7 +233,6 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_ordered_kernel(RoiBwdOrdArgs
 }  // namespace relnet
 
 using namespace relnet;
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
 
 static int launch_roi_pool(const RoiArgs& g, int dtype, bool aligned, void* stream, const char* what) {
   dim3 grid((unsigned)((long)g.R * g.PH * g.PW));
@@ -347,7 +339,7 @@ __global__ __launch_bounds__(kOwnerThreads) void roi_pool_bwd_owner_kernel(RoiBw
       for (int e = 0; e < 4; ++e) { v[2 * e] = bf2f(w4[e] & 0xffff); v[2 * e + 1] = bf2f(w4[e] >> 16); }
     } else {
 #pragma unroll
-      for (int e = 0; e < CH; ++e) v[e] = ld<T>((const T*)g.grad_out + o + e);
+      for (int e = 0; e < CH; ++e) v[e] = ldf<T>((const T*)g.grad_out + o + e);
     }
   };
   auto add = [&](const int (&a)[CH], const float (&v)[CH]) {

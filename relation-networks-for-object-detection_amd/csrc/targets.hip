@@ -4,6 +4,8 @@
 // 24-74).  In the reference each of these is a numpy CustomOp behind an .asnumpy() host round trip
 // (three of the four syncs per training step); here they are small integer / float64 kernels.
 #include "common.h"
+#include "ordering.h"
+#include "wave.h"
 
 namespace relnet {
 
@@ -117,11 +119,6 @@ struct OhemArgs {
   int R, C, D, roi_per_img;
 };
 
-__device__ __forceinline__ unsigned int fkey_t(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(1024) void ohem_kernel(OhemArgs g) {
   __shared__ unsigned long long keys[2048];
   __shared__ unsigned short rank_of[2048];
@@ -153,23 +150,12 @@ __global__ __launch_bounds__(1024) void ohem_kernel(OhemArgs g) {
         tot = lc + (float)lb;
       }
       if (g.loss) g.loss[(long)b * g.R + r] = tot;
-      key = ((unsigned long long)fkey_t(tot) << 16) | (unsigned)r;               // ties: larger index first
+      key = ((unsigned long long)order_key(tot) << 16) | (unsigned)r;               // ties: larger index first
     }
     keys[r] = key;
   }
   __syncthreads();
-  for (int k = 2; k <= np2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < np2; i += 1024) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], d = keys[ixj];
-          const bool desc = (i & k) == 0;
-          if (desc ? (a < d) : (a > d)) { keys[i] = d; keys[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_desc<1024>(keys, np2);
   for (int i = tid; i < g.R; i += 1024) rank_of[(int)(keys[i] & 0xffffu)] = (unsigned short)i;
   __syncthreads();
   for (int r = tid; r < g.R; r += 1024) {
@@ -393,8 +379,7 @@ __global__ __launch_bounds__(1024) void anchor_sample_kernel(AnchorArgs g) {
   auto block_count = [&](float want) -> int {
     int c = 0;
     for (int p = tid; p < total; p += 1024) c += lab[p] == want ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum(c);
     __syncthreads();
     if (lane == 0) s_red[wave] = c;
     __syncthreads();
@@ -521,8 +506,7 @@ __global__ __launch_bounds__(kPtsThreads) void proposal_target_sample_kernel(PTS
     return (float)b;
   };
   auto block_sum = [&](int c) -> int {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum(c);
     __syncthreads();
     if (lane == 0) s_red[wave] = c;
     __syncthreads();

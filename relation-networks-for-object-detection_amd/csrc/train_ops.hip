@@ -8,9 +8,9 @@
 //                         mom = momentum * mom - lr * (rescale * grad + wd * w);  w += mom
 //                       on fp32 master weights, optionally refreshing a bf16 copy for the MFMA kernels.
 #include "common.h"
+#include "wave.h"
 
 namespace relnet {
-enum { RELNET_F32 = 0, RELNET_BF16 = 1 };
 
 template <typename T>
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const T* dy, const T* y, const T* add, T* dx, long n) {
@@ -317,8 +317,7 @@ __global__ __launch_bounds__(256) void reduce_scalar_kernel(const float* x, long
   float acc = 0.f;
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) acc += mode ? (x[i] >= 0.f ? 1.f : 0.f) : x[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(out, (mode ? 1.f : scale) * (part[0] + part[1] + part[2] + part[3]));
@@ -414,8 +413,7 @@ __global__ __launch_bounds__(256) void reduce_scalar_ordered_partial_kernel(cons
   float acc = 0.f;
   const long stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) acc += mode ? (x[i] >= 0.f ? 1.f : 0.f) : x[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) sp[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = (mode ? 1.f : scale) * (((sp[0] + sp[1]) + sp[2]) + sp[3]);
