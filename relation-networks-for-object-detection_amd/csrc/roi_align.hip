@@ -11,6 +11,7 @@
 // Explicit element strides like csrc/roi_pool.hip: NCHW fp32 (parity tests) and channels-last bf16 (thread = (bin, 8 channels), four 16-byte
 // corner loads per sample).  Arithmetic in fp32 with contraction off, in the order oracle/roi_align.py restates: bit-identical on fp32 data.
 #include "common.h"
+#include "roi.h"
 
 namespace relnet {
 
@@ -46,23 +47,22 @@ __device__ __forceinline__ RoiBin roi_bin(const RoiAlignArgs& g, int r, float sc
   return q;
 }
 
-// The map of roi r as plain scalars.  Constant indices only: a dynamic index into the kernarg array forces a scratch copy of the struct
-// (csrc/roi_pool.hip:roi_map).  ok == false: invalid batch index or level -> the caller writes zeros / adds nothing (the fields then
-// describe level 0 and are not dereferenced).
+// The map of roi r as plain scalars (RELNET_LV_SEL4: constant indices only).  ok == false: invalid batch index or level -> the caller
+// writes zeros / adds nothing (the fields then describe level 0 and are not dereferenced).
 struct RoiAlignMap { const void* data; long ds_b, ds_c, ds_h, ds_w; float* grad; long gs_b, gs_c, gs_h, gs_w; int H, W; float scale; bool ok; };
-#define RA_SEL4(l, f) ((l) == 0 ? g.lv[0].f : (l) == 1 ? g.lv[1].f : (l) == 2 ? g.lv[2].f : g.lv[3].f)
 __device__ __forceinline__ RoiAlignMap roi_align_map(const RoiAlignArgs& g, int r) {
   RoiAlignMap m;
   int l = g.level ? g.level[r] : 0;
   const int b = (int)g.rois[(long)r * 5] - g.batch_index_base;
   m.ok = l >= 0 && l < g.num_levels && b >= 0 && b < g.B;
   if (!m.ok) l = 0;
-  m.data = RA_SEL4(l, data); m.ds_b = RA_SEL4(l, ds_b); m.ds_c = RA_SEL4(l, ds_c); m.ds_h = RA_SEL4(l, ds_h); m.ds_w = RA_SEL4(l, ds_w);
-  m.grad = RA_SEL4(l, grad); m.gs_b = RA_SEL4(l, gs_b); m.gs_c = RA_SEL4(l, gs_c); m.gs_h = RA_SEL4(l, gs_h); m.gs_w = RA_SEL4(l, gs_w);
-  m.H = RA_SEL4(l, H); m.W = RA_SEL4(l, W); m.scale = RA_SEL4(l, scale);
+#define LV(f) RELNET_LV_SEL4(g, l, f)
+  m.data = LV(data); m.ds_b = LV(ds_b); m.ds_c = LV(ds_c); m.ds_h = LV(ds_h); m.ds_w = LV(ds_w);
+  m.grad = LV(grad); m.gs_b = LV(gs_b); m.gs_c = LV(gs_c); m.gs_h = LV(gs_h); m.gs_w = LV(gs_w);
+  m.H = LV(H); m.W = LV(W); m.scale = LV(scale);
+#undef LV
   return m;
 }
-#undef RA_SEL4
 
 // the four corners and weights of one sample; returns false when the sample lies outside the map (contributes 0)
 struct Corners { int yl, xl, yh, xh; float w1, w2, w3, w4; };
@@ -95,9 +95,9 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(RoiAlignArgs g) {
     const T* pc = base + (long)c * m.ds_c;
     float sum = 0.f;
     for (int iy = 0; iy < q.grid_h; ++iy) {
-      const float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
+      const float y = roi_align_coord(q.start_h, ph, q.bin_h, iy, q.grid_h);
       for (int ix = 0; ix < q.grid_w; ++ix) {
-        const float x = q.start_w + (float)pw * q.bin_w + ((float)ix + 0.5f) * q.bin_w / (float)q.grid_w;
+        const float x = roi_align_coord(q.start_w, pw, q.bin_w, ix, q.grid_w);
         Corners k;
         if (!corners(y, x, m.H, m.W, k)) continue;
         const float v1 = ldf<T>(pc + (long)k.yl * m.ds_h + (long)k.xl * m.ds_w), v2 = ldf<T>(pc + (long)k.yl * m.ds_h + (long)k.xh * m.ds_w);
@@ -127,9 +127,9 @@ __global__ __launch_bounds__(256) void roi_align_fwd_cl_kernel(RoiAlignArgs g, i
     const RoiBin q = roi_bin(g, r, m.scale);
     const unsigned short* base = (const unsigned short*)m.data + (long)q.b * m.ds_b + cg * 8;
     for (int iy = 0; iy < q.grid_h; ++iy) {
-      const float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
+      const float y = roi_align_coord(q.start_h, ph, q.bin_h, iy, q.grid_h);
       for (int ix = 0; ix < q.grid_w; ++ix) {
-        const float x = q.start_w + (float)pw * q.bin_w + ((float)ix + 0.5f) * q.bin_w / (float)q.grid_w;
+        const float x = roi_align_coord(q.start_w, pw, q.bin_w, ix, q.grid_w);
         Corners k;
         if (!corners(y, x, m.H, m.W, k)) continue;
         const uint4 a1 = *(const uint4*)(base + (long)k.yl * m.ds_h + (long)k.xl * m.ds_w), a2 = *(const uint4*)(base + (long)k.yl * m.ds_h + (long)k.xh * m.ds_w);
@@ -162,9 +162,9 @@ __global__ __launch_bounds__(256) void roi_align_bwd_kernel(RoiAlignArgs g) {
     const float go = ldf<T>((const T*)g.out + (long)r * g.os_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw) / q.count;
     float* gc = gb + (long)c * g.gs_c;
     for (int iy = 0; iy < q.grid_h; ++iy) {
-      const float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
+      const float y = roi_align_coord(q.start_h, ph, q.bin_h, iy, q.grid_h);
       for (int ix = 0; ix < q.grid_w; ++ix) {
-        const float x = q.start_w + (float)pw * q.bin_w + ((float)ix + 0.5f) * q.bin_w / (float)q.grid_w;
+        const float x = roi_align_coord(q.start_w, pw, q.bin_w, ix, q.grid_w);
         Corners k;
         if (!corners(y, x, g.H, g.W, k)) continue;
         atomicAdd(gc + (long)k.yl * g.gs_h + (long)k.xl * g.gs_w, k.w1 * go);
@@ -199,58 +199,16 @@ __global__ __launch_bounds__(256) void roi_align_bwd_levels_kernel(RoiAlignArgs 
     // footprint: the cell range every valid sample's corners cover, per axis
     if (threadIdx.x < 2) { s_lo[threadIdx.x] = INT_MAX; s_hi[threadIdx.x] = -1; }
     __syncthreads();
-    for (int s = threadIdx.x; s < PP * q.grid_h; s += 256) {
-      const int ph = s / q.grid_h, iy = s % q.grid_h;
-      float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
-      if (y < -1.f || y > (float)m.H) continue;
-      if (y <= 0.f) y = 0.f;
-      const int yl = min((int)y, m.H - 1), yh = min(yl + 1, m.H - 1);
-      atomicMin(&s_lo[0], yl); atomicMax(&s_hi[0], yh);
-    }
-    for (int s = threadIdx.x; s < PP * q.grid_w; s += 256) {
-      const int pw = s / q.grid_w, ix = s % q.grid_w;
-      float x = q.start_w + (float)pw * q.bin_w + ((float)ix + 0.5f) * q.bin_w / (float)q.grid_w;
-      if (x < -1.f || x > (float)m.W) continue;
-      if (x <= 0.f) x = 0.f;
-      const int xl = min((int)x, m.W - 1), xh = min(xl + 1, m.W - 1);
-      atomicMin(&s_lo[1], xl); atomicMax(&s_hi[1], xh);
-    }
+    roi_align_axis_footprint(q.start_h, q.bin_h, q.grid_h, PP, m.H, &s_lo[0], &s_hi[0]);
+    roi_align_axis_footprint(q.start_w, q.bin_w, q.grid_w, PP, m.W, &s_lo[1], &s_hi[1]);
     __syncthreads();
     const int y0 = s_lo[0], x0 = s_lo[1];
     const int FH = s_hi[0] - y0 + 1, FW = s_hi[1] - x0 + 1;
     if (FH <= 0 || FW <= 0) return;                      // no sample inside the map: no gradient
     if (FH <= RA_PATCH_MAX && FW <= RA_PATCH_MAX && (long)FH * FW <= 4L * q.grid_h * q.grid_w * PP * PP) {
       // per-axis weight sums, in a fixed order (deterministic); 1/count folded into the rows
-      for (int s = threadIdx.x; s < PP * FH; s += 256) {
-        const int ph = s / FH, cell = y0 + s % FH;
-        float w = 0.f;
-        for (int iy = 0; iy < q.grid_h; ++iy) {
-          float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
-          if (y < -1.f || y > (float)m.H) continue;
-          if (y <= 0.f) y = 0.f;
-          int yl = (int)y, yh;
-          if (yl >= m.H - 1) { yh = yl = m.H - 1; y = (float)yl; } else yh = yl + 1;
-          const float ly = y - (float)yl;
-          if (yl == cell) w += 1.f - ly;
-          if (yh == cell) w += ly;
-        }
-        s_wy[ph * RA_PATCH_MAX + s % FH] = w / q.count;
-      }
-      for (int s = threadIdx.x; s < PP * FW; s += 256) {
-        const int pw = s / FW, cell = x0 + s % FW;
-        float w = 0.f;
-        for (int ix = 0; ix < q.grid_w; ++ix) {
-          float x = q.start_w + (float)pw * q.bin_w + ((float)ix + 0.5f) * q.bin_w / (float)q.grid_w;
-          if (x < -1.f || x > (float)m.W) continue;
-          if (x <= 0.f) x = 0.f;
-          int xl = (int)x, xh;
-          if (xl >= m.W - 1) { xh = xl = m.W - 1; x = (float)xl; } else xh = xl + 1;
-          const float lx = x - (float)xl;
-          if (xl == cell) w += 1.f - lx;
-          if (xh == cell) w += lx;
-        }
-        s_wx[pw * RA_PATCH_MAX + s % FW] = w;
-      }
+      roi_align_axis_weights(q.start_h, q.bin_h, q.grid_h, PP, m.H, y0, FH, q.count, s_wy, RA_PATCH_MAX);
+      roi_align_axis_weights(q.start_w, q.bin_w, q.grid_w, PP, m.W, x0, FW, 1.f, s_wx, RA_PATCH_MAX);
       __syncthreads();
       for (int c = threadIdx.x; c < g.C; c += 256) {
         float go[PP * PP];
@@ -285,9 +243,9 @@ __global__ __launch_bounds__(256) void roi_align_bwd_levels_kernel(RoiAlignArgs 
       for (int pw = 0; pw < g.PW; ++pw) {
         const float go = ldf<T>(go_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw) / q.count;
         for (int iy = 0; iy < q.grid_h; ++iy) {
-          const float y = q.start_h + (float)ph * q.bin_h + ((float)iy + 0.5f) * q.bin_h / (float)q.grid_h;
+          const float y = roi_align_coord(q.start_h, ph, q.bin_h, iy, q.grid_h);
           for (int ix = 0; ix < q.grid_w; ++ix) {
-            const float x = q.start_w + (float)pw * q.bin_w + ((float)ix + 0.5f) * q.bin_w / (float)q.grid_w;
+            const float x = roi_align_coord(q.start_w, pw, q.bin_w, ix, q.grid_w);
             Corners k;
             if (!corners(y, x, m.H, m.W, k)) continue;
             atomicAdd(gc + (long)k.yl * m.gs_h + (long)k.xl * m.gs_w, k.w1 * go);
@@ -369,11 +327,11 @@ static int fill_levels(RoiAlignArgs& g, const long* strides4_levels, const int* 
                        int num_levels, const char* what) {
   RELNET_REQUIRE(strides4_levels && heights && widths && spatial_scales, "%s: null operand", what);
   RELNET_REQUIRE(num_levels >= 1 && num_levels <= 4, "%s: 1..4 pyramid levels, got %d", what, num_levels);
-  for (int l = 0; l < 4; ++l) {
-    const int s = l < num_levels ? l : num_levels - 1;
+  if (roi_fill_levels(num_levels, [&](int l, int s) {
     RELNET_REQUIRE(heights[s] > 0 && widths[s] > 0, "%s: bad level %d", what, s);
     g.lv[l].H = heights[s]; g.lv[l].W = widths[s]; g.lv[l].scale = spatial_scales[s];
-  }
+    return 0;
+  })) return -1;
   g.num_levels = num_levels;
   return 0;
 }
@@ -387,12 +345,12 @@ extern "C" int relnet_roi_align_levels_fwd(const void* const* data_levels, const
   RELNET_REQUIRE(R >= 0 && B > 0 && C > 0 && PH > 0 && PW > 0, "%s: bad shape", what);
   RoiAlignArgs g{};
   if (fill_levels(g, data_strides4_levels, heights, widths, spatial_scales, num_levels, what)) return -1;
-  for (int l = 0; l < 4; ++l) {
-    const int s = l < num_levels ? l : num_levels - 1;
+  if (roi_fill_levels(num_levels, [&](int l, int s) {
     RELNET_REQUIRE(data_levels[s], "%s: null level %d", what, s);
     g.lv[l].data = data_levels[s]; g.lv[l].ds_b = data_strides4_levels[4 * s]; g.lv[l].ds_c = data_strides4_levels[4 * s + 1];
     g.lv[l].ds_h = data_strides4_levels[4 * s + 2]; g.lv[l].ds_w = data_strides4_levels[4 * s + 3];
-  }
+    return 0;
+  })) return -1;
   g.rois = rois; g.out = out; g.os_r = out_strides4[0]; g.os_c = out_strides4[1]; g.os_ph = out_strides4[2]; g.os_pw = out_strides4[3];
   g.R = R; g.C = C; g.PH = PH; g.PW = PW; g.sampling_ratio = sampling_ratio; g.aligned = aligned;
   g.batch_index_base = batch_index_base; g.level = roi_level; g.B = B;
@@ -409,12 +367,12 @@ extern "C" int relnet_roi_align_levels_bwd(const void* grad_out, const long* out
   RELNET_REQUIRE(R >= 0 && B > 0 && C > 0 && PH > 0 && PW > 0, "%s: bad shape", what);
   RoiAlignArgs g{};
   if (fill_levels(g, grad_strides4_levels, heights, widths, spatial_scales, num_levels, what)) return -1;
-  for (int l = 0; l < 4; ++l) {
-    const int s = l < num_levels ? l : num_levels - 1;
+  if (roi_fill_levels(num_levels, [&](int l, int s) {
     RELNET_REQUIRE(grad_levels[s], "%s: null level %d", what, s);
     g.lv[l].grad = grad_levels[s]; g.lv[l].gs_b = grad_strides4_levels[4 * s]; g.lv[l].gs_c = grad_strides4_levels[4 * s + 1];
     g.lv[l].gs_h = grad_strides4_levels[4 * s + 2]; g.lv[l].gs_w = grad_strides4_levels[4 * s + 3];
-  }
+    return 0;
+  })) return -1;
   g.rois = rois; g.out = const_cast<void*>(grad_out);
   g.os_r = out_strides4[0]; g.os_c = out_strides4[1]; g.os_ph = out_strides4[2]; g.os_pw = out_strides4[3];
   g.R = R; g.C = C; g.PH = PH; g.PW = PW; g.sampling_ratio = sampling_ratio; g.aligned = aligned;

@@ -4,6 +4,7 @@
 // parity tests) and channels-last bf16 (the throughput path, where the 256 channels of a
 // bin are contiguous and a wavefront reads 64 consecutive channels per pixel).
 #include "common.h"
+#include "roi.h"
 #include <float.h>
 
 namespace relnet {
@@ -23,14 +24,14 @@ struct RoiArgs {
 // Feature map of roi r as plain scalars (rois are level-sorted and r is uniform per workgroup, so this is a uniform
 // kernarg read; the kernel-argument struct itself is never written -- doing so spills it to scratch, 6x slower).
 struct RoiMap { const void* data; long ds_b, ds_c, ds_h, ds_w; int H, W; float scale; };
-#define RELNET_SEL4(l, f) ((l) == 0 ? g.lv[0].f : (l) == 1 ? g.lv[1].f : (l) == 2 ? g.lv[2].f : g.lv[3].f)
 __device__ __forceinline__ RoiMap roi_map(const RoiArgs& g, int r) {
   RoiMap m;
-  if (g.level) {         // constant indices only: a dynamic index into the kernarg array forces a scratch copy of the struct
+  if (g.level) {         // (RELNET_LV_SEL4: constant indices only)
     const int l = g.level[r] & 3;
-    m.data = RELNET_SEL4(l, data); m.ds_b = RELNET_SEL4(l, ds_b); m.ds_c = RELNET_SEL4(l, ds_c);
-    m.ds_h = RELNET_SEL4(l, ds_h); m.ds_w = RELNET_SEL4(l, ds_w); m.H = RELNET_SEL4(l, H); m.W = RELNET_SEL4(l, W);
-    m.scale = RELNET_SEL4(l, scale);
+#define LV(f) RELNET_LV_SEL4(g, l, f)
+    m.data = LV(data); m.ds_b = LV(ds_b); m.ds_c = LV(ds_c); m.ds_h = LV(ds_h); m.ds_w = LV(ds_w); m.H = LV(H); m.W = LV(W);
+    m.scale = LV(scale);
+#undef LV
   } else {
     m.data = g.data; m.ds_b = g.ds_b; m.ds_c = g.ds_c; m.ds_h = g.ds_h; m.ds_w = g.ds_w; m.H = g.H; m.W = g.W; m.scale = g.scale;
   }
@@ -46,14 +47,10 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(RoiArgs g) {
   const RoiMap m = roi_map(g, r);
   const float* roi = g.rois + (long)r * 5;
   const int b = (int)roi[0] - g.batch_index_base;
-  const int rs_w = (int)roundf(roi[1] * m.scale), rs_h = (int)roundf(roi[2] * m.scale);
-  const int re_w = (int)roundf(roi[3] * m.scale), re_h = (int)roundf(roi[4] * m.scale);
-  const int rw = max(re_w - rs_w + 1, 1), rh = max(re_h - rs_h + 1, 1);   // malformed -> 1x1
-  const float bin_h = (float)rh / (float)g.PH, bin_w = (float)rw / (float)g.PW;
-  int hs = (int)floorf((float)ph * bin_h), he = (int)ceilf((float)(ph + 1) * bin_h);
-  int ws = (int)floorf((float)pw * bin_w), we = (int)ceilf((float)(pw + 1) * bin_w);
-  hs = min(max(hs + rs_h, 0), m.H); he = min(max(he + rs_h, 0), m.H);
-  ws = min(max(ws + rs_w, 0), m.W); we = min(max(we + rs_w, 0), m.W);
+  const RoiWindow q = roi_window(roi, m.scale, g.PH, g.PW);
+  int hs, he, ws, we;
+  roi_bin_span(ph, q.rs_h, q.bin_h, m.H, hs, he);
+  roi_bin_span(pw, q.rs_w, q.bin_w, m.W, ws, we);
   const bool empty = (he <= hs) || (we <= ws);
   const T* base = (const T*)m.data + (long)b * m.ds_b;
   for (int c = threadIdx.x; c < g.C; c += 256) {
@@ -84,14 +81,10 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_cl_kernel(RoiArgs g) {
   const RoiMap m = roi_map(g, r);
   const float* roi = g.rois + (long)r * 5;
   const int b = (int)roi[0] - g.batch_index_base;
-  const int rs_w = (int)roundf(roi[1] * m.scale), rs_h = (int)roundf(roi[2] * m.scale);
-  const int re_w = (int)roundf(roi[3] * m.scale), re_h = (int)roundf(roi[4] * m.scale);
-  const int rw = max(re_w - rs_w + 1, 1), rh = max(re_h - rs_h + 1, 1);
-  const float bin_h = (float)rh / (float)g.PH, bin_w = (float)rw / (float)g.PW;
-  int hs = (int)floorf((float)ph * bin_h), he = (int)ceilf((float)(ph + 1) * bin_h);
-  int ws = (int)floorf((float)pw * bin_w), we = (int)ceilf((float)(pw + 1) * bin_w);
-  hs = min(max(hs + rs_h, 0), m.H); he = min(max(he + rs_h, 0), m.H);
-  ws = min(max(ws + rs_w, 0), m.W); we = min(max(we + rs_w, 0), m.W);
+  const RoiWindow q = roi_window(roi, m.scale, g.PH, g.PW);
+  int hs, he, ws, we;
+  roi_bin_span(ph, q.rs_h, q.bin_h, m.H, hs, he);
+  roi_bin_span(pw, q.rs_w, q.bin_w, m.W, ws, we);
   const bool empty = (he <= hs) || (we <= ws);
   float best[8];
   int bi[8];
@@ -137,7 +130,8 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_kernel(RoiBwdArgs g) {
   float* gin = g.grad_in; long ds_b = g.ds_b, ds_c = g.ds_c, ds_p = g.ds_p;
   if (g.level) {
     const int l = g.level[r] & 3;
-    gin = RELNET_SEL4(l, grad_in); ds_b = RELNET_SEL4(l, ds_b); ds_c = RELNET_SEL4(l, ds_c); ds_p = RELNET_SEL4(l, ds_p);
+    gin = RELNET_LV_SEL4(g, l, grad_in); ds_b = RELNET_LV_SEL4(g, l, ds_b); ds_c = RELNET_LV_SEL4(g, l, ds_c);
+    ds_p = RELNET_LV_SEL4(g, l, ds_p);
   }
   for (int c = threadIdx.x; c < g.C; c += 256) {
     const long o = (long)r * g.os_r + (long)c * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw;
@@ -172,9 +166,10 @@ __device__ __forceinline__ bool roi_bin_range(int y, int rs, int rn, int P, floa
   hi = min((int)ceilf((float)(rel + 1) / bin), P - 1);
   return lo <= hi;
 }
-// does bin p of that axis hold cell y?  (roi_pool_fwd_kernel's arithmetic, L = the map's extent)
+// does bin p of that axis hold cell y?  (the forward's own span, L = the map's extent)
 __device__ __forceinline__ bool roi_bin_holds(int p, int y, int rs, float bin, int L) {
-  const int s = min(max((int)floorf((float)p * bin) + rs, 0), L), e = min(max((int)ceilf((float)(p + 1) * bin) + rs, 0), L);
+  int s, e;
+  roi_bin_span(p, rs, bin, L, s, e);
   return y >= s && y < e;
 }
 
@@ -193,16 +188,13 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_ordered_kernel(RoiBwdOrdArgs
   for (int r = 0; r < g.R; ++r) {
     const float* roi = g.rois + (long)r * 5;
     if ((int)roi[0] - g.batch_index_base != b) continue;
-    const int rs_w = (int)roundf(roi[1] * g.scale), rs_h = (int)roundf(roi[2] * g.scale);
-    const int re_w = (int)roundf(roi[3] * g.scale), re_h = (int)roundf(roi[4] * g.scale);
-    const int rw = max(re_w - rs_w + 1, 1), rh = max(re_h - rs_h + 1, 1);
-    const float bin_h = (float)rh / (float)g.PH, bin_w = (float)rw / (float)g.PW;
+    const RoiWindow q = roi_window(roi, g.scale, g.PH, g.PW);
     int ph0, ph1, pw0, pw1;
-    if (!roi_bin_range(y, rs_h, rh, g.PH, bin_h, ph0, ph1) || !roi_bin_range(x, rs_w, rw, g.PW, bin_w, pw0, pw1)) continue;
+    if (!roi_bin_range(y, q.rs_h, q.rh, g.PH, q.bin_h, ph0, ph1) || !roi_bin_range(x, q.rs_w, q.rw, g.PW, q.bin_w, pw0, pw1)) continue;
     for (int ph = ph0; ph <= ph1; ++ph) {
-      if (!roi_bin_holds(ph, y, rs_h, bin_h, g.H)) continue;
+      if (!roi_bin_holds(ph, y, q.rs_h, q.bin_h, g.H)) continue;
       for (int pw = pw0; pw <= pw1; ++pw) {
-        if (!roi_bin_holds(pw, x, rs_w, bin_w, g.W)) continue;
+        if (!roi_bin_holds(pw, x, q.rs_w, q.bin_w, g.W)) continue;
         const long o = (long)r * g.os_r + (long)c0 * g.os_c + (long)ph * g.os_ph + (long)pw * g.os_pw;
         if constexpr (VEC == 8) {
           const int4 a0 = *(const int4*)(g.argmax + o), a1 = *(const int4*)(g.argmax + o + 4);
@@ -277,14 +269,14 @@ extern "C" int relnet_roi_pool_fpn_fwd(const void* const* data_levels, const lon
   RELNET_REQUIRE(R > 0 && C > 0 && PH > 0 && PW > 0, "relnet_roi_pool_fpn_fwd: bad shape");
   RoiArgs g;
   bool aligned = true;
-  for (int l = 0; l < 4; ++l) {
-    const int s = l < num_levels ? l : num_levels - 1;
+  if (roi_fill_levels(num_levels, [&](int l, int s) {
     RELNET_REQUIRE(data_levels[s] && heights[s] > 0 && widths[s] > 0, "relnet_roi_pool_fpn_fwd: bad level %d", s);
     g.lv[l].data = data_levels[s]; g.lv[l].ds_b = data_strides4_levels[4 * s]; g.lv[l].ds_c = data_strides4_levels[4 * s + 1];
     g.lv[l].ds_h = data_strides4_levels[4 * s + 2];
     g.lv[l].ds_w = data_strides4_levels[4 * s + 3]; g.lv[l].H = heights[s]; g.lv[l].W = widths[s]; g.lv[l].scale = spatial_scales[s];
     aligned = aligned && g.lv[l].ds_c == 1 && g.lv[l].ds_b % 8 == 0 && g.lv[l].ds_h % 8 == 0 && g.lv[l].ds_w % 8 == 0;
-  }
+    return 0;
+  })) return -1;
   g.data = g.lv[0].data; g.ds_b = g.lv[0].ds_b; g.ds_c = data_strides4_levels[1]; g.ds_h = g.lv[0].ds_h; g.ds_w = g.lv[0].ds_w;
   g.H = g.lv[0].H; g.W = g.lv[0].W; g.scale = g.lv[0].scale;
   g.rois = rois; g.out = out; g.os_r = out_strides4[0]; g.os_c = out_strides4[1]; g.os_ph = out_strides4[2]; g.os_pw = out_strides4[3];
@@ -478,12 +470,12 @@ extern "C" int relnet_roi_pool_fpn_bwd_ex(const void* grad_out, const int* argma
   RoiBwdArgs g{grad_out, argmax, out_strides4[0], out_strides4[1], out_strides4[2], out_strides4[3],
                rois, grad_in_levels[0], gs_b_levels[0], gs_c_levels[0], R, C, 0, PH, PW, batch_index_base, roi_level, {},
                gs_p_levels ? gs_p_levels[0] : 1};
-  for (int l = 0; l < 4; ++l) {
-    const int s = l < num_levels ? l : num_levels - 1;
+  if (roi_fill_levels(num_levels, [&](int l, int s) {
     RELNET_REQUIRE(grad_in_levels[s], "relnet_roi_pool_fpn_bwd: null level %d", s);
     g.lv[l].grad_in = grad_in_levels[s]; g.lv[l].ds_b = gs_b_levels[s]; g.lv[l].ds_c = gs_c_levels[s];
     g.lv[l].ds_p = gs_p_levels ? gs_p_levels[s] : 1;
-  }
+    return 0;
+  })) return -1;
   dim3 grid((unsigned)((long)R * PH * PW));
   if (dtype == RELNET_F32) roi_pool_bwd_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(g);
   else if (dtype == RELNET_BF16) roi_pool_bwd_kernel<unsigned short><<<grid, 256, 0, (hipStream_t)stream>>>(g);

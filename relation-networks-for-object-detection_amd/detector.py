@@ -15,6 +15,7 @@ from . import ops
 from .backbone import Backbone, PIXEL_MEANS
 from .relation import RelationHead
 from .learn_nms import LearnNMS
+from .pooling import RoiPooling, check_pooling      # (check_pooling: also importable from here)
 from .operator_py.proposal import generate_anchors, propose_batch
 
 
@@ -101,13 +102,6 @@ def fc1_channels_last_perm(c=256, ph=7, pw=7):
     return (ch * (ph * pw) + s).reshape(-1)
 
 
-def check_pooling(cfg):
-    """cfg.roi_align together with cfg.dcn: the DCN graph pools with deformable PSROI pooling (SYM_DCN_RELNMS:1073-1080), there is no
-    ROIAlign in it to switch to -- refused rather than silently ignored."""
-    if getattr(cfg, 'roi_align', False) and getattr(cfg, 'dcn', False):
-        raise ValueError("roi_align and dcn cannot be combined: the DCN graph pools with deformable PSROI pooling")
-
-
 def check_box_regression(cfg, params):
     """bbox_pred_weight and cfg.class_agnostic must agree: 4 * num_classes rows are a class-specific head (num_reg_classes = num_classes,
     symbols/...:157), anything else the class-agnostic one (8 rows; with num_classes == 2 the two layouts coincide).  A class-specific
@@ -125,7 +119,7 @@ class Detector(object):
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', cfg=None, relation=True,
                  im_hw=(600, 1000), stem='hip'):
         self.cfg = cfg or Config()
-        check_pooling(self.cfg)
+        self.pool = RoiPooling(self.cfg, (1.0 / self.cfg.feat_stride,))
         check_box_regression(self.cfg, params)
         self.dtype, self.device, self.relation, self.im_hw = dtype, device, relation, im_hw
         self.overlap_rpn = True
@@ -180,21 +174,10 @@ class Detector(object):
             f = self.backbone.forward(data, im_info=im_info)
             rois, roi_scores, num_kept = propose(f['rpn_cls_score'], f['rpn_bbox_pred'])
         N = rois.shape[1]
-        if c.dcn:                 # SYM_DCN_RELNMS:1073-1080
-            feat, r5, sc = f['conv_new_1_relu'], rois.view(B * N, 5), 1.0 / c.feat_stride
-            t0 = ops.deformable_psroi_pool(feat, r5, None, sc, feat.shape[1], 1, 7, 7, c.dcn_sample_per_part, 0.0, True,
-                                           channels_last_out=True)
-            trans = ops.gemm_nt(t0.permute(0, 2, 3, 1).reshape(B * N, -1), self.w_offset, self.b_offset,
-                                out_dtype=torch.float32).view(B * N, 2, 7, 7)
-            pooled = ops.deformable_psroi_pool(feat, r5, trans, sc, feat.shape[1], 1, 7, 7, c.dcn_sample_per_part,
-                                               c.dcn_trans_std, False, channels_last_out=True)
-        elif c.roi_align:
-            pooled = ops.roi_align(f['conv_new_1_relu'], rois.view(B * N, 5), (7, 7), 1.0 / c.feat_stride, c.roi_align_sampling,
-                                   channels_last_out=True)
-        else:
-            pooled = ops.roi_pool(f['conv_new_1_relu'], rois.view(B * N, 5), (7, 7), 1.0 / c.feat_stride,
-                                  channels_last_out=True)
-        pooled = pooled.permute(0, 2, 3, 1).reshape(B, N, -1)              # (ph, pw, c) order, no copy
+        offset_fc = None
+        if c.dcn:
+            offset_fc = lambda t0f: ops.gemm_nt(t0f, self.w_offset, self.b_offset, out_dtype=torch.float32)
+        pooled = self.pool.forward([f['conv_new_1_relu']], rois.view(B * N, 5), offset_fc=offset_fc).view(B, N, -1)
         if keep_features and self.relation:
             hd = self.head.forward(pooled, rois, return_intermediates=True)
             cls_score, bbox_pred, feat = hd['cls_score'], hd['bbox_pred'], hd['fc_all_2_relu']
@@ -293,6 +276,7 @@ class FPNDetector(object):
 
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', cfg=None, relation=True, stem='hip'):
         self.cfg = cfg or Config()
+        self.pool = RoiPooling(self.cfg, self.scales)
         check_box_regression(self.cfg, params)
         self.dtype, self.device = dtype, device
         self.backbone = Backbone(params, dtype, device, stem=stem, fpn=True, pixel_means=self.cfg.pixel_means)
@@ -323,12 +307,7 @@ class FPNDetector(object):
             rois, level, perm, counts = ops.fpn_roi_dispatch(proposals.contiguous())
         N = rois.shape[1]
         lv = [f['fpn_ft4'], f['fpn_ft8'], f['fpn_ft16'], f['fpn_ft32']]
-        if c.roi_align:
-            pooled = ops.roi_align_fpn(lv, self.scales, rois.view(B * N, 5), level.view(-1), (7, 7), c.roi_align_sampling,
-                                       channels_last_out=True)
-        else:
-            pooled = ops.roi_pool_fpn(lv, self.scales, rois.view(B * N, 5), level.view(-1), (7, 7), channels_last_out=True)
-        pooled = pooled.permute(0, 2, 3, 1).reshape(B, N, -1)
+        pooled = self.pool.forward(lv, rois.view(B * N, 5), level.view(-1)).view(B, N, -1)
         cls_score, bbox_pred, feat = self.head.forward(pooled, rois, key_count=n_rows)
         out = dict(rois=rois, roi_level=level, perm=perm, level_counts=counts, num_rows=n_rows, cls_score=cls_score,
                    bbox_pred=bbox_pred, fc_all_2_relu=feat)

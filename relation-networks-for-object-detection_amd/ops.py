@@ -326,6 +326,39 @@ def nms_greedy(det, thresh, post, counts=None, want_keep=False, batch_index_base
     return dict(rois=rois, scores=rscores, keep=keep, num_keep=num)
 
 
+def _pooled_out(R, C, PH, PW, channels_last_out, device, dtype):
+    """Uninitialised pooled features, logical [R,C,PH,PW]; memory order (R,PH,PW,C) when channels_last_out."""
+    if channels_last_out:
+        return torch.empty((R, PH, PW, C), device=device, dtype=dtype).permute(0, 3, 1, 2)
+    return torch.empty((R, C, PH, PW), device=device, dtype=dtype)
+
+
+def _map_grads(shapes, channels_last, device, zero=True):
+    """One fp32 gradient per (B,C,H,W) in `shapes`, logical [B,C,H,W]; memory NHWC when channels_last.  Zero-filled for the kernels that
+    accumulate with atomics; zero=False leaves them uninitialised for the ordered form, which writes every word."""
+    new = torch.zeros if zero else torch.empty
+    if channels_last:
+        return [new((B, H, W, C), device=device, dtype=torch.float32).permute(0, 3, 1, 2) for B, C, H, W in shapes]
+    return [new((B, C, H, W), device=device, dtype=torch.float32) for B, C, H, W in shapes]
+
+
+def _level_arrays(ts, scales):
+    """ctypes arrays of the levels entry points: data pointers, 4 element strides per map, heights, widths, spatial scales."""
+    import ctypes
+    n = len(ts)
+    return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]), (ctypes.c_long * (4 * n))(*[int(s) for t in ts for s in t.stride()]),
+            (ctypes.c_int * n)(*[int(t.shape[2]) for t in ts]), (ctypes.c_int * n)(*[int(t.shape[3]) for t in ts]),
+            (ctypes.c_float * n)(*[float(x) for x in scales]))
+
+
+def _level_stride_triples(ts):
+    """The sibling for the ROIPooling adjoint: data pointers and the (image, channel, pixel) element strides, one array each."""
+    import ctypes
+    n = len(ts)
+    return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]),) + tuple(
+        (ctypes.c_long * n)(*[int(t.stride(d)) for t in ts]) for d in (0, 1, 3))
+
+
 def roi_pool(data, rois, pooled=(7, 7), spatial_scale=0.0625, channels_last_out=False,
              want_argmax=False, batch_index_base=0):
     """data: logical [B,C,H,W] tensor of any strides (NCHW or channels_last memory format);
@@ -336,10 +369,7 @@ def roi_pool(data, rois, pooled=(7, 7), spatial_scale=0.0625, channels_last_out=
     B, Cc, H, W = data.shape
     R = rois.shape[0]
     PH, PW = pooled
-    if channels_last_out:
-        out = torch.empty((R, PH, PW, Cc), device=data.device, dtype=data.dtype).permute(0, 3, 1, 2)
-    else:
-        out = torch.empty((R, Cc, PH, PW), device=data.device, dtype=data.dtype)
+    out = _pooled_out(R, Cc, PH, PW, channels_last_out, data.device, data.dtype)
     arg = torch.empty_strided(out.shape, out.stride(), device=data.device, dtype=torch.int32) if want_argmax else None
     _lib.call('relnet_roi_pool_fwd', data.data_ptr(), _strides4(data), rois.data_ptr(), out.data_ptr(),
               _strides4(out), _ptr(arg), R, Cc, H, W, PH, PW, float(spatial_scale), batch_index_base,
@@ -357,23 +387,17 @@ def roi_pool_bwd(grad_out, argmax, rois, in_shape, batch_index_base=0, channels_
     assert argmax.dtype == torch.int32 and tuple(grad_out.stride()) == tuple(argmax.stride()) and grad_out.shape == argmax.shape
     B, Cc, H, W = in_shape
     R, _, PH, PW = grad_out.shape
+    gin, = _map_grads([in_shape], channels_last, grad_out.device, zero=not deterministic)
     if deterministic:
         assert rois.dtype == torch.float32 and rois.is_contiguous()
-        if channels_last:
-            gin = torch.empty((B, H, W, Cc), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2)        # every word is written
-        else:
-            gin = torch.empty((B, Cc, H, W), device=grad_out.device, dtype=torch.float32)
         _lib.call('relnet_roi_pool_bwd_ordered', grad_out.data_ptr(), argmax.data_ptr(), _strides4(grad_out), rois.data_ptr(), gin.data_ptr(),
                   gin.stride(0), gin.stride(1), gin.stride(3), B, H, W, R, Cc, PH, PW, float(spatial_scale), batch_index_base, _dt(grad_out), _stream())
         return gin
     if channels_last:
-        gin = torch.zeros((B, H, W, Cc), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2)
         # (relnet_roi_pool_bwd_cl: from 8 images x 256 channels up, one workgroup per (image, 8 channels) accumulates its slab in LDS -- no global atomics)
         _lib.call('relnet_roi_pool_bwd_cl', grad_out.data_ptr(), argmax.data_ptr(), _strides4(grad_out), rois.data_ptr(), gin.data_ptr(),
                   B, H, W, R, Cc, PH, PW, batch_index_base, _dt(grad_out), _stream())
         return gin
-    else:
-        gin = torch.zeros((B, Cc, H, W), device=grad_out.device, dtype=torch.float32)
     _lib.call('relnet_roi_pool_bwd_ex', grad_out.data_ptr(), argmax.data_ptr(), _strides4(grad_out), rois.data_ptr(),
               gin.data_ptr(), gin.stride(0), gin.stride(1), gin.stride(3), R, Cc, W, PH, PW, batch_index_base, _dt(grad_out), _stream())
     return gin
@@ -389,10 +413,7 @@ def roi_align(data, rois, pooled=(7, 7), spatial_scale=0.0625, sampling_ratio=2,
     B, Cc, H, W = data.shape
     R = rois.shape[0]
     PH, PW = pooled
-    if channels_last_out:
-        out = torch.empty((R, PH, PW, Cc), device=data.device, dtype=data.dtype).permute(0, 3, 1, 2)
-    else:
-        out = torch.empty((R, Cc, PH, PW), device=data.device, dtype=data.dtype)
+    out = _pooled_out(R, Cc, PH, PW, channels_last_out, data.device, data.dtype)
     _lib.call('relnet_roi_align_fwd', data.data_ptr(), _strides4(data), rois.data_ptr(), out.data_ptr(), _strides4(out), R, Cc, H, W,
               PH, PW, float(spatial_scale), int(sampling_ratio), int(bool(aligned)), batch_index_base, _dt(data), _stream())
     return out
@@ -405,10 +426,7 @@ def roi_align_bwd(grad_out, rois, in_shape, spatial_scale=0.0625, sampling_ratio
     _chk(grad_out, rois)
     B, Cc, H, W = in_shape
     R, _, PH, PW = grad_out.shape
-    if channels_last:
-        gin = torch.zeros((B, H, W, Cc), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2)
-    else:
-        gin = torch.zeros((B, Cc, H, W), device=grad_out.device, dtype=torch.float32)
+    gin, = _map_grads([in_shape], channels_last, grad_out.device)
     _lib.call('relnet_roi_align_bwd', grad_out.data_ptr(), _strides4(grad_out), rois.data_ptr(), gin.data_ptr(), _strides4(gin), R, Cc,
               H, W, PH, PW, float(spatial_scale), int(sampling_ratio), int(bool(aligned)), batch_index_base, _dt(grad_out), _stream())
     return gin
@@ -1186,10 +1204,7 @@ def deformable_psroi_pool(data, rois, trans=None, spatial_scale=0.0625, output_d
         part = part_size or P
         num_classes = trans.shape[1] // 2
         assert tuple(trans.shape) == (R, 2 * num_classes, part, part), trans.shape
-    if channels_last_out:
-        out = torch.empty((R, P, P, output_dim), device=data.device, dtype=data.dtype).permute(0, 3, 1, 2)
-    else:
-        out = torch.empty((R, output_dim, P, P), device=data.device, dtype=data.dtype)
+    out = _pooled_out(R, int(output_dim), P, P, channels_last_out, data.device, data.dtype)
     cnt = torch.empty_strided(out.shape, out.stride(), device=data.device, dtype=torch.float32) if want_top_count else None
     _lib.call('relnet_deformable_psroi_pool_fwd', data.data_ptr(), _strides4(data), rois.data_ptr(),
               0 if no_trans else trans.data_ptr(), out.data_ptr(), _strides4(out), _ptr(cnt), R, Cc, H, W,
@@ -1234,17 +1249,10 @@ def roi_pool_fpn(levels, scales, rois, roi_level, pooled=(7, 7), channels_last_o
     Cc = levels[0].shape[1]
     R = rois.shape[0]
     PH, PW = pooled
-    ptrs = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in levels])
-    strides = (ctypes.c_long * (4 * nl))(*[int(s) for t in levels for s in t.stride()])
-    hs = (ctypes.c_int * nl)(*[int(t.shape[2]) for t in levels])
-    ws = (ctypes.c_int * nl)(*[int(t.shape[3]) for t in levels])
-    sc = (ctypes.c_float * nl)(*[float(x) for x in scales])
+    ptrs, strides, hs, ws, sc = _level_arrays(levels, scales)
     dt = levels[0].dtype
     assert all(t.dtype == dt and t.shape[1] == Cc for t in levels)
-    if channels_last_out:
-        out = torch.empty((R, PH, PW, Cc), device=rois.device, dtype=dt).permute(0, 3, 1, 2)
-    else:
-        out = torch.empty((R, Cc, PH, PW), device=rois.device, dtype=dt)
+    out = _pooled_out(R, Cc, PH, PW, channels_last_out, rois.device, dt)
     arg = torch.empty_strided(out.shape, out.stride(), device=rois.device, dtype=torch.int32) if want_argmax else None
     _lib.call('relnet_roi_pool_fpn_fwd', ctypes.addressof(ptrs), ctypes.addressof(strides), ctypes.addressof(hs),
               ctypes.addressof(ws), ctypes.addressof(sc), nl, rois.data_ptr(), roi_level.data_ptr(), out.data_ptr(),
@@ -1259,27 +1267,13 @@ def roi_pool_fpn_bwd(grad_out, argmax, rois, roi_level, level_shapes, batch_inde
     _chk(grad_out, argmax, rois, roi_level)
     assert argmax.dtype == torch.int32 and tuple(grad_out.stride()) == tuple(argmax.stride())
     R, Cc, PH, PW = grad_out.shape
-    if channels_last:
-        gins = [torch.zeros((sh[0], sh[2], sh[3], sh[1]), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2) for sh in level_shapes]
-    else:
-        gins = [torch.zeros(tuple(sh), device=grad_out.device, dtype=torch.float32) for sh in level_shapes]
+    gins = _map_grads(level_shapes, channels_last, grad_out.device)
     nl = len(gins)
-    ptrs = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in gins])
-    gb = (ctypes.c_long * nl)(*[int(t.stride(0)) for t in gins])
-    gc = (ctypes.c_long * nl)(*[int(t.stride(1)) for t in gins])
-    gp = (ctypes.c_long * nl)(*[int(t.stride(3)) for t in gins])
+    ptrs, gb, gc, gp = _level_stride_triples(gins)
     _lib.call('relnet_roi_pool_fpn_bwd_ex', grad_out.data_ptr(), argmax.data_ptr(), _strides4(grad_out), rois.data_ptr(),
               roi_level.data_ptr(), ctypes.addressof(ptrs), ctypes.addressof(gb), ctypes.addressof(gc), ctypes.addressof(gp),
               nl, R, Cc, PH, PW, batch_index_base, _dt(grad_out), _stream())
     return gins
-
-
-def _level_arrays(ts, scales):
-    import ctypes
-    n = len(ts)
-    return ((ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]), (ctypes.c_long * (4 * n))(*[int(s) for t in ts for s in t.stride()]),
-            (ctypes.c_int * n)(*[int(t.shape[2]) for t in ts]), (ctypes.c_int * n)(*[int(t.shape[3]) for t in ts]),
-            (ctypes.c_float * n)(*[float(x) for x in scales]))
 
 
 def roi_align_fpn(levels, scales, rois, roi_level=None, pooled=(7, 7), sampling_ratio=2, aligned=False, channels_last_out=False,
@@ -1297,10 +1291,7 @@ def roi_align_fpn(levels, scales, rois, roi_level=None, pooled=(7, 7), sampling_
     assert all(t.dtype == dt and t.shape[0] == B and t.shape[1] == Cc for t in levels)
     R = rois.shape[0]
     PH, PW = pooled
-    if channels_last_out:
-        out = torch.empty((R, PH, PW, Cc), device=rois.device, dtype=dt).permute(0, 3, 1, 2)
-    else:
-        out = torch.empty((R, Cc, PH, PW), device=rois.device, dtype=dt)
+    out = _pooled_out(R, Cc, PH, PW, channels_last_out, rois.device, dt)
     ptrs, strides, hs, ws, sc = _level_arrays(levels, scales)
     _lib.call('relnet_roi_align_levels_fwd', ctypes.addressof(ptrs), ctypes.addressof(strides), ctypes.addressof(hs), ctypes.addressof(ws),
               ctypes.addressof(sc), len(levels), rois.data_ptr(), _ptr(roi_level), out.data_ptr(), _strides4(out), R, B, Cc, PH, PW,
@@ -1317,10 +1308,7 @@ def roi_align_fpn_bwd(grad_out, rois, roi_level, level_shapes, scales, sampling_
     assert rois.dtype == torch.float32 and rois.is_contiguous() and len(level_shapes) == len(scales)
     assert roi_level is None or (roi_level.dtype == torch.int32 and roi_level.is_contiguous() and roi_level.numel() == rois.shape[0])
     R, Cc, PH, PW = grad_out.shape
-    if channels_last:
-        gins = [torch.zeros((sh[0], sh[2], sh[3], sh[1]), device=grad_out.device, dtype=torch.float32).permute(0, 3, 1, 2) for sh in level_shapes]
-    else:
-        gins = [torch.zeros(tuple(sh), device=grad_out.device, dtype=torch.float32) for sh in level_shapes]
+    gins = _map_grads(level_shapes, channels_last, grad_out.device)
     assert all(t.shape[0] == gins[0].shape[0] and t.shape[1] == Cc for t in gins)
     ptrs, strides, hs, ws, sc = _level_arrays(gins, scales)
     _lib.call('relnet_roi_align_levels_bwd', grad_out.data_ptr(), _strides4(grad_out), rois.data_ptr(), _ptr(roi_level),

@@ -28,7 +28,8 @@ from . import ops, losses, train_ops as T
 from . import dist as D
 from .backbone import unit_names, conv_bn_names, fold_bn, EPS
 from .relation import attention_module_backward, _module_forward, pack_pair_pos, GradSink
-from .detector import Config, fc1_channels_last_perm, check_pooling
+from .detector import Config, fc1_channels_last_perm
+from .pooling import RoiPooling
 from .operator_py.proposal import generate_anchors, propose_batch
 
 
@@ -221,17 +222,17 @@ class Trainer(object):
         rpn_cls_prob, rpn_label, cls_prob, nms_conditional_score and the loss tensors behind the loss scalars (rpn_bbox_loss_map, bbox_loss_map,
         nms_pos_loss_map, nms_neg_loss_map): the output list of the reference's train graph, which metric.py's host classes take."""
         self.cfg = cfg or TrainConfig()
-        check_pooling(self.cfg)
-        check_deterministic(self.cfg)
+        check_deterministic(self.cfg)       # (its user-facing messages come before the pooler's assertions)
+        c = self.cfg
+        self.deterministic = bool(getattr(c, 'deterministic', False))       # read ONCE: every site below routes on this attribute
+        self.fpn = bool(getattr(c, 'fpn', False))
+        self.pool = RoiPooling(c, self.scales if self.fpn else (1.0 / c.feat_stride,), deterministic=self.deterministic)
         check_batch_rois(self.cfg)
         check_box_head(self.cfg, params)
         self.device, self.im_hw = device, im_hw
-        c = self.cfg
         self.class_agnostic = bool(getattr(c, 'class_agnostic', True))
-        self.deterministic = bool(getattr(c, 'deterministic', False))       # read ONCE: every site below routes on this attribute
         dev = device
         f32 = lambda t: torch.as_tensor(t).to(dev, torch.float32).contiguous()
-        self.fpn = bool(getattr(c, 'fpn', False))
         self.relation = bool(getattr(c, 'relation', True))
         # cfg.trunk_fp32 (parity tests only): conv1 .. res5 forward AND backward in float32 on the exact-fp32 MFMA kernels
         # (relnet_conv2d_nhwc_f32 / relnet_gemm_nt f32, master weights read directly, no chain kernels, no fused ReLU-mask epilogue) with
@@ -660,22 +661,9 @@ class Trainer(object):
                 if torch.is_tensor(v) and v.is_cuda:
                     v.record_stream(main)
         rois_t, label, bbox_target, bbox_weight, N, R = (br[k] for k in ('rois_t', 'label', 'bbox_target', 'bbox_weight', 'N', 'R'))
-        r5 = rois_t.view(B * R, 5)
-        if c.dcn:
-            sc_ = 1.0 / c.feat_stride
-            t0 = ops.deformable_psroi_pool(nchw(feat), r5, None, sc_, feat.shape[3], 1, 7, 7, c.dcn_sample_per_part, 0.0, True,
-                                           channels_last_out=True)
-            t0f = t0.permute(0, 2, 3, 1).reshape(B * R, -1)
-            trans = ops.gemm_nt(t0f, self.w('offset'), self.b('offset'), out_dtype=torch.float32).view(B * R, 2, 7, 7)
-            pooled = ops.deformable_psroi_pool(nchw(feat), r5, trans, sc_, feat.shape[3], 1, 7, 7, c.dcn_sample_per_part,
-                                               c.dcn_trans_std, False, channels_last_out=True)
-            argmax = None
-        elif c.roi_align:           # one map, no level table: the single-map case of the levels kernels
-            pooled = ops.roi_align_fpn([nchw(feat)], [1.0 / c.feat_stride], r5, None, (7, 7), c.roi_align_sampling, channels_last_out=True)
-            argmax = None
-        else:
-            pooled, argmax = ops.roi_pool(nchw(feat), r5, (7, 7), 1.0 / c.feat_stride, channels_last_out=True, want_argmax=True)
-        pooled2 = pooled.permute(0, 2, 3, 1).reshape(B * R, -1)
+        # (the offset FC's weights are views of the flat buffers that change every step: read when called)
+        offset_fc = lambda t0f: ops.gemm_nt(t0f, self.w('offset'), self.b('offset'), out_dtype=torch.float32)
+        pooled2, pool_ctx = self.pool.forward([nchw(feat)], rois_t.view(B * R, 5), offset_fc=offset_fc, want_backward=True)
         d_pool, hs = self._head_forward_backward(pooled2, rois_t, N, label, bbox_target, bbox_weight, im_info, gt_boxes, num_gt, out)
         bt = torch.bfloat16
         x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem = hs
@@ -685,26 +673,12 @@ class Trainer(object):
             out['bbox_target'], out['bbox_weight'] = bbox_target, weights_ohem
             out['bbox_pred'], out['cls_score'], out['fc_all_2_relu'] = bbox_pred, cls_score, x2
             return out
-        # ROIPooling / ROIAlign backward -> gradient of conv_new_1_relu
-        if c.dcn:
-            gp = d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2)
-            gd1, gtrans = ops.deformable_psroi_pool_bwd(gp, nchw(feat), r5, trans, sc_, feat.shape[3], 1, 7, 7,
-                                                        c.dcn_sample_per_part, c.dcn_trans_std, False)
-            d_t0, dw, db = T.linear_bwd(t0f, self.w('offset'), gtrans.view(B * R, -1).to(bt), w_t=self.wt('offset'), keep_splits=True, wgrad_to=self._wg('offset'))
+        # pooling backward -> gradient of conv_new_1_relu (the offset FC's parameter gradients go to this trainer's queues)
+        def offset_fc_bwd(t0f, g_trans):
+            d_t0, dw, db = T.linear_bwd(t0f, self.w('offset'), g_trans.to(bt), w_t=self.wt('offset'), keep_splits=True, wgrad_to=self._wg('offset'))
             self._add_bgrad('offset', db)
-            gd2, _ = ops.deformable_psroi_pool_bwd(d_t0.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), nchw(feat), r5, None, sc_,
-                                                   feat.shape[3], 1, 7, 7, c.dcn_sample_per_part, 0.0, True)
-            d_feat = (gd1 + gd2).permute(0, 2, 3, 1).to(bt).contiguous()       # logical NCHW stored NHWC -> NHWC bf16
-        elif c.roi_align:
-            d_feat, = ops.roi_align_fpn_bwd(d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), r5, None,
-                                            [(B, feat.shape[3], feat.shape[1], feat.shape[2])], [1.0 / c.feat_stride], c.roi_align_sampling,
-                                            channels_last=True)
-            d_feat = d_feat.permute(0, 2, 3, 1).to(bt)          # NHWC memory already: one conversion pass
-        else:
-            d_feat = ops.roi_pool_bwd(d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2), argmax, r5,
-                                      (B, feat.shape[3], feat.shape[1], feat.shape[2]), channels_last=True,
-                                      deterministic=self.deterministic, spatial_scale=1.0 / c.feat_stride)
-            d_feat = d_feat.permute(0, 2, 3, 1).to(bt)          # NHWC memory already: one conversion pass
+            return d_t0
+        d_feat, = self.pool.backward(d_pool, pool_ctx, offset_fc_bwd)
         g = T.relu_bwd(d_feat, feat)
         d_x, dw = T.conv1x1_bwd(conv5, self.w('conv_new_1'), g, w_t=self.wt('conv_new_1'), keep_splits=True, wgrad_to=self._wg('conv_new_1'))
         T.colsum_add(g, *self._bg('conv_new_1'))
@@ -1497,27 +1471,13 @@ class FPNTrainer(Trainer):
             perm = torch.cat([pa, pb + N], 1).long()
         gat = lambda t: torch.gather(t, 1, perm.view(B, R, *([1] * (t.dim() - 2))).expand(B, R, *t.shape[2:]))
         label, bbox_target, bbox_weight = gat(label), gat(bbox_target).contiguous(), gat(bbox_weight).contiguous()
-        nchw = lambda t: t.permute(0, 3, 1, 2)
-        lv = [nchw(feats[4]), nchw(feats[8]), nchw(feats[16]), nchw(feats[32])]
-        if c.roi_align:
-            pooled = ops.roi_align_fpn(lv, self.scales, rois_s.view(B * R, 5), level.view(-1), (7, 7), c.roi_align_sampling,
-                                       channels_last_out=True)
-        else:
-            pooled, argmax = ops.roi_pool_fpn(lv, self.scales, rois_s.view(B * R, 5), level.view(-1), (7, 7), channels_last_out=True,
-                                              want_argmax=True)
-        pooled2 = pooled.permute(0, 2, 3, 1).reshape(B * R, -1)
+        lv = [feats[lvl].permute(0, 3, 1, 2) for lvl in (4, 8, 16, 32)]
+        pooled2, pool_ctx = self.pool.forward(lv, rois_s.view(B * R, 5), level.view(-1), want_backward=True)
         d_pool, hs = self._head_forward_backward(pooled2, rois_s, N, label.contiguous(), bbox_target, bbox_weight, im_info,
                                                  gt_boxes, num_gt, out, key_count=key_count)
         x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem = hs
         # ---- pooling backward into the four pyramid maps
-        d_pool4 = d_pool.view(B * R, 7, 7, -1).permute(0, 3, 1, 2)
-        if c.roi_align:
-            g_lv = ops.roi_align_fpn_bwd(d_pool4, rois_s.view(B * R, 5), level.view(-1), [tuple(t.shape) for t in lv], self.scales,
-                                         c.roi_align_sampling, channels_last=True)
-        else:
-            g_lv = ops.roi_pool_fpn_bwd(d_pool4, argmax, rois_s.view(B * R, 5), level.view(-1), [tuple(t.shape) for t in lv],
-                                        channels_last=True)
-        d_feats = {lvl: g.permute(0, 2, 3, 1).to(bt) for lvl, g in zip((4, 8, 16, 32), g_lv)}
+        d_feats = dict(zip((4, 8, 16, 32), self.pool.backward(d_pool, pool_ctx)))
         # ---- neck backward (top-down pathway reversed: finest level first, gradients flow up to the coarser tops)
         d_tops, inject, d_c5 = {}, {}, None
         for lvl in (4, 8, 16, 32):
