@@ -115,6 +115,25 @@ def check_box_regression(cfg, params):
                          % (rows, 4 * cfg.num_classes))
 
 
+def _postprocess(out, cfg, cls_score, bbox_pred, rois, im_info, N, post, n_valid=None):
+    """Tail of both test graphs without the learn-NMS head (core/tester.py:148-156,244-277): softmax + decode -> cls_prob [B,N,C], pred_boxes
+    [B,N,4] ([B,N,C,4] class-specific) and, with `post`, per-class (soft-)NMS + the image's max_per_image cut, added to `out`.
+    n_valid [B] int32: rows past it are padding (zero probabilities and boxes)."""
+    B = cls_score.shape[0]
+    prob, boxes = ops.detect_head(cls_score.reshape(B * N, -1), bbox_pred.reshape(B * N, -1),
+                                  rois.view(B * N, 5), im_info, N, n_valid=n_valid, class_agnostic=cfg.class_agnostic)
+    out['cls_prob'], out['pred_boxes'] = prob.view(B, N, -1), boxes.view((B, N) + tuple(boxes.shape[1:]))       # [B,N,4], or [B,N,C,4] class-specific
+    if post:
+        # (top_k: a class list stops once its next pick cannot reach the image's max_per_image best scores -- the lists are
+        #  prefixes of the full per-class lists that contain everything image_topk keeps: relnet_class_nms_topk)
+        dets, counts = ops.class_nms(out['cls_prob'], out['pred_boxes'], cfg.score_thresh, cfg.nms, cfg.softnms,
+                                     max_picks=cfg.max_per_image, top_k=cfg.max_per_image)
+        det, det_count, thresh, total = ops.image_topk(dets, counts, cfg.max_per_image)
+        out.update(class_dets=dets, class_counts=counts, detections=det, num_detections=det_count,
+                   image_thresh=thresh)
+    return out
+
+
 class Detector(object):
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', cfg=None, relation=True,
                  im_hw=(600, 1000), stem='hip'):
@@ -136,10 +155,7 @@ class Detector(object):
                                  use_relation=relation)
         self.lnms = None
         if self.cfg.learn_nms:
-            self.lnms = LearnNMS(params, self.cfg.num_classes - 1, self.cfg.first_n, len(self.cfg.nms_target_thresh),
-                                 self.cfg.learn_nms_class_thresh, None, None, self.cfg.merge_method,
-                                 self.cfg.score_thresh, self.cfg.max_per_image, dtype=dtype, device=device,
-                                 class_agnostic=self.cfg.class_agnostic)
+            self.lnms = LearnNMS.from_config(params, self.cfg, dtype, device)
         self.anchors = torch.as_tensor(generate_anchors(self.cfg.feat_stride, self.cfg.anchor_ratios,
                                                         self.cfg.anchor_scales), dtype=torch.float64, device=device)
 
@@ -190,18 +206,7 @@ class Detector(object):
         if self.lnms is not None and post:                 # symbols/..._learn_nms.py:518-565 + tester.py:231-242
             out.update(self.lnms.forward(cls_score.contiguous(), bbox_pred.contiguous(), rois, im_info, feat))
             return out
-        prob, boxes = ops.detect_head(cls_score.reshape(B * N, -1), bbox_pred.reshape(B * N, -1),
-                                      rois.view(B * N, 5), im_info, N, class_agnostic=c.class_agnostic)
-        out['cls_prob'], out['pred_boxes'] = prob.view(B, N, -1), boxes.view((B, N) + tuple(boxes.shape[1:]))       # [B,N,4], or [B,N,C,4] class-specific
-        if post:
-            # (top_k: a class list stops once its next pick cannot reach the image's max_per_image best scores -- the lists are
-            #  prefixes of the full per-class lists that contain everything image_topk keeps: relnet_class_nms_topk)
-            dets, counts = ops.class_nms(out['cls_prob'], out['pred_boxes'], c.score_thresh, c.nms, c.softnms,
-                                         max_picks=c.max_per_image, top_k=c.max_per_image)
-            det, det_count, thresh, total = ops.image_topk(dets, counts, c.max_per_image)
-            out.update(class_dets=dets, class_counts=counts, detections=det, num_detections=det_count,
-                       image_thresh=thresh)
-        return out
+        return _postprocess(out, c, cls_score, bbox_pred, rois, im_info, N, post)
 
 
 
@@ -284,10 +289,7 @@ class FPNDetector(object):
                                  fc_names=('roi_pool_fc1', 'roi_pool_fc2'))
         self.lnms = None
         if self.cfg.learn_nms:
-            self.lnms = LearnNMS(params, self.cfg.num_classes - 1, self.cfg.first_n, len(self.cfg.nms_target_thresh),
-                                 self.cfg.learn_nms_class_thresh, None, None, self.cfg.merge_method,
-                                 self.cfg.score_thresh, self.cfg.max_per_image, dtype=dtype, device=device,
-                                 class_agnostic=self.cfg.class_agnostic)
+            self.lnms = LearnNMS.from_config(params, self.cfg, dtype, device)
 
     pad_empty_levels = True
 
@@ -314,12 +316,4 @@ class FPNDetector(object):
         if self.lnms is not None and post:
             out.update(self.lnms.forward(cls_score.contiguous(), bbox_pred.contiguous(), rois, im_info, feat, n_valid=n_rows))
             return out
-        prob, boxes = ops.detect_head(cls_score.reshape(B * N, -1), bbox_pred.reshape(B * N, -1),
-                                      rois.view(B * N, 5), im_info, N, n_valid=n_rows, class_agnostic=c.class_agnostic)
-        out['cls_prob'], out['pred_boxes'] = prob.view(B, N, -1), boxes.view((B, N) + tuple(boxes.shape[1:]))
-        if post:
-            dets, cnts = ops.class_nms(out['cls_prob'], out['pred_boxes'], c.score_thresh, c.nms, c.softnms,
-                                       max_picks=c.max_per_image, top_k=c.max_per_image)
-            det, det_count, thresh, total = ops.image_topk(dets, cnts, c.max_per_image)
-            out.update(class_dets=dets, class_counts=cnts, detections=det, num_detections=det_count, image_thresh=thresh)
-        return out
+        return _postprocess(out, c, cls_score, bbox_pred, rois, im_info, N, post, n_valid=n_rows)

@@ -2,6 +2,7 @@
 all arithmetic happens in librelnet_hip.so).  Every function requires CUDA(HIP) tensors
 and raises otherwise -- there is no CPU or eager fallback.
 """
+import ctypes
 import math
 import os
 
@@ -522,6 +523,234 @@ def image_topk(dets, counts, max_per_image=100, max_out=None):
     _lib.call('relnet_image_topk', dets.data_ptr(), counts.data_ptr(), thresh.data_ptr(), total.data_ptr(),
               out.data_ptr(), out_count.data_ptr(), B, NC, N, max_per_image, max_out, _stream())
     return out, out_count, thresh, total
+
+
+# ---------------------------------------------------------------------------------------
+# learn-NMS head (csrc/learn_nms.hip: the stages of both branches; csrc/lnms_train.hip: the element-wise chains of the train branch and
+# of its adjoint).  Every check below reads shapes, dtypes and strides only: these run inside hipGraph capture.
+# ---------------------------------------------------------------------------------------
+def _dense(t, shape, dtype):
+    """t is a contiguous `dtype` tensor of exactly `shape`."""
+    assert tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.is_contiguous(), (tuple(t.shape), t.dtype, t.stride(), tuple(shape), dtype)
+
+
+def _float4(v):
+    """means4 / stds4 of the prepare kernels: a HOST array of 4 floats, None -> NULL."""
+    if v is None:
+        return None
+    v = [float(x) for x in v]
+    assert len(v) == 4, v
+    return (ctypes.c_float * 4)(*v)
+
+
+def lnms_prepare(cls_score, bbox_pred, rois, im_info, class_agnostic=True, means=None, stds=None, n_valid=None, delta_off=4, out=None):
+    """cls_score [B,N,C+1] fp32 logits, bbox_pred [B,N,4*num_reg] fp32 (rows of both: one free stride), rois [B,N,5], im_info [B,3]
+    -> prob [B,N,C] fp32 (softmax, background dropped), boxes [B,N,4] fp32 refined from columns delta_off..delta_off+3 and clipped;
+    class_agnostic=False: bbox_pred is [B,N,4*(C+1)], foreground class k is refined from its own columns 4(k+1).. -> boxes [B,N,C,4].
+    means / stds: 4 floats each or None (learn_nms.py:420-421).  n_valid [B] int32: rows past it are padding (probability 0, zero boxes).
+    out = (prob, boxes) pre-allocated."""
+    _chk(cls_score, bbox_pred, rois, im_info, n_valid)
+    B, N, C1 = cls_score.shape
+    assert cls_score.dtype == torch.float32 and bbox_pred.dtype == torch.float32 and C1 > 1
+    assert bbox_pred.dim() == 3 and tuple(bbox_pred.shape[:2]) == (B, N)
+    for t in (cls_score, bbox_pred):
+        assert t.stride(2) == 1 and (B == 1 or t.stride(0) == N * t.stride(1)) and t.stride(1) >= t.shape[2], (t.shape, t.stride())
+    _dense(rois, (B, N, 5), torch.float32)
+    _dense(im_info, (B, 3), torch.float32)
+    if n_valid is not None:
+        _dense(n_valid, (B,), torch.int32)
+    means, stds = _float4(means), _float4(stds)
+    if class_agnostic:
+        assert 0 <= delta_off and delta_off + 4 <= bbox_pred.shape[2], (delta_off, bbox_pred.shape)
+    elif bbox_pred.shape[2] != 4 * C1:
+        raise ValueError("class-specific bbox_pred must have 4 * %d columns, got %d" % (C1, bbox_pred.shape[2]))
+    box_shape = (B, N, 4) if class_agnostic else (B, N, C1 - 1, 4)
+    if out is None:
+        out = (torch.empty((B, N, C1 - 1), device=cls_score.device, dtype=torch.float32),
+               torch.empty(box_shape, device=cls_score.device, dtype=torch.float32))
+    prob, boxes = out
+    _chk(prob, boxes)
+    _dense(prob, (B, N, C1 - 1), torch.float32)
+    _dense(boxes, box_shape, torch.float32)
+    head = (cls_score.data_ptr(), cls_score.stride(1), bbox_pred.data_ptr(), bbox_pred.stride(1), rois.data_ptr(), im_info.data_ptr(),
+            prob.data_ptr(), boxes.data_ptr(), B, N, C1)
+    if class_agnostic:
+        _lib.call('relnet_lnms_prepare_ex', *head, int(delta_off), means, stds, _ptr(n_valid), _stream())
+    else:
+        _lib.call('relnet_lnms_prepare_cs', *head, means, stds, _ptr(n_valid), _stream())
+    return prob, boxes
+
+
+def lnms_sort(prob, boxes, first_n, out=None):
+    """prob [B,N,C] fp32, boxes [B,N,4] (one box per roi) or [B,N,C,4] (class-specific) fp32 -> per (image, class) descending sort, first_n
+    ranks (ties: smaller roi index first): rank_idx [B,C,F] int32, sorted_score [B,F,C], sorted_bbox [B,F,C,4], class_boxes [B,C,F,4],
+    class_max [B,C].  first_n <= N <= 1024.  out = those five, pre-allocated."""
+    _chk(prob, boxes)
+    B, N, C = prob.shape
+    F = int(first_n)
+    _dense(prob, (B, N, C), torch.float32)
+    _dense(boxes, (B, N, C, 4) if boxes.dim() == 4 else (B, N, 4), torch.float32)
+    assert 0 < F <= N <= 1024, "need first_n <= N <= 1024, got first_n %d, N %d" % (F, N)
+    shapes = ((B, C, F), (B, F, C), (B, F, C, 4), (B, C, F, 4), (B, C))
+    if out is None:
+        out = tuple(torch.empty(s, device=prob.device, dtype=torch.int32 if i == 0 else torch.float32) for i, s in enumerate(shapes))
+    assert len(out) == 5
+    _chk(*out)
+    for i, (t, s) in enumerate(zip(out, shapes)):
+        _dense(t, s, torch.int32 if i == 0 else torch.float32)
+    _lib.call('relnet_lnms_sort_cs' if boxes.dim() == 4 else 'relnet_lnms_sort', prob.data_ptr(), boxes.data_ptr(), *[t.data_ptr() for t in out],
+              B, N, C, F, _stream())
+    return tuple(out)
+
+
+def _ranks(rank_idx):
+    """rank_idx [B,C,F] int32 (dense) -> B, C, F."""
+    assert rank_idx.dim() == 3
+    _dense(rank_idx, rank_idx.shape, torch.int32)
+    return tuple(rank_idx.shape)
+
+
+def lnms_embed(roi_emb, rank_feat, rank_idx, out=None):
+    """x[b,c,r,:] = roi_emb[b, rank_idx[b,c,r], :] + rank_feat[r, :] (learn_nms.py:335-344).  roi_emb [B*N,D] or [B,N,D] bf16 / fp32
+    (N >= F: the ranks address its first rows), rank_feat [F,D] fp32, rank_idx [B,C,F] int32 -> x [B,C,F,D] in roi_emb's dtype."""
+    _chk(roi_emb, rank_feat, rank_idx, out)
+    B, C, F = _ranks(rank_idx)
+    D = roi_emb.shape[-1]
+    rows = roi_emb.numel() // D
+    assert roi_emb.is_contiguous() and roi_emb.dim() in (2, 3) and rows % B == 0 and D % 8 == 0, (roi_emb.shape, B)
+    N = rows // B
+    assert N >= F, "ranks of first_n %d address %d rows" % (F, N)
+    _dense(rank_feat, (F, D), torch.float32)
+    if out is None:
+        out = torch.empty((B, C, F, D), device=roi_emb.device, dtype=roi_emb.dtype)
+    _dense(out, (B, C, F, D), roi_emb.dtype)
+    _lib.call('relnet_lnms_embed', roi_emb.data_ptr(), rank_feat.data_ptr(), rank_idx.data_ptr(), out.data_ptr(), B, N, C, F, D, _dt(out), _stream())
+    return out
+
+
+def lnms_score(x, att, w_logit, b_logit, sorted_score, sorted_bbox, class_max, im_info, merge=-1, class_thresh=0.01, score_thresh=1e-3,
+               want_detections=True):
+    """Test-branch tail (learn_nms.py:349-381 + tester.py:231-242): relu(x + attention), logit FC, sigmoid, x sorted_score (0 for the classes
+    that fail the valid-class rule), merge over the T = 5 thresholds, compaction of score > score_thresh.  x [B,C,F,128] and att [B*C,F,1024]
+    (16 heads x 64, 8 real columns each) bf16 / fp32, w_logit [5,128] / b_logit [5] fp32, sorted_score [B,F,C], sorted_bbox [B,F,C,4],
+    class_max [B,C], im_info [B,3] -> multi [B,F,C,5], final [B,F,C], dets [B,C,F,5] float64 and counts [B,C] int32 (None, None unless
+    want_detections)."""
+    _chk(x, att, w_logit, b_logit, sorted_score, sorted_bbox, class_max, im_info)
+    B, C, F, D = x.shape
+    T, H, dv, hstride = 5, 16, 8, 64
+    assert D == H * dv and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16), (x.shape, x.dtype)
+    _dense(att, (B * C, F, H * hstride), x.dtype)
+    _dense(w_logit, (T, D), torch.float32)
+    _dense(b_logit, (T,), torch.float32)
+    _dense(sorted_score, (B, F, C), torch.float32)
+    _dense(sorted_bbox, (B, F, C, 4), torch.float32)
+    _dense(class_max, (B, C), torch.float32)
+    _dense(im_info, (B, 3), torch.float32)
+    dev = x.device
+    multi = torch.empty((B, F, C, T), device=dev, dtype=torch.float32)
+    final = torch.empty((B, F, C), device=dev, dtype=torch.float32)
+    dets = torch.zeros((B, C, F, 5), device=dev, dtype=torch.float64) if want_detections else None
+    counts = torch.empty((B, C), device=dev, dtype=torch.int32) if want_detections else None
+    _lib.call('relnet_lnms_score', x.data_ptr(), att.data_ptr(), w_logit.data_ptr(), b_logit.data_ptr(), sorted_score.data_ptr(),
+              sorted_bbox.data_ptr(), class_max.data_ptr(), im_info.data_ptr(), multi.data_ptr(), final.data_ptr(), _ptr(dets), _ptr(counts),
+              B, C, F, D, T, H, dv, hstride, int(merge), float(class_thresh), float(score_thresh), _dt(x), _stream())
+    return multi, final, dets, counts
+
+
+def lnms_pad_params(wo, bo, wl, bl, wout_pad, bout_pad, wl_pad, bl_pad):
+    """nms_linear_out_1 [128,128] bf16 / bias [128] and nms_logit [T,128] bf16 / bias [T] (T <= 64) into the real rows of the zero-padded
+    operands of the 64-wide tiles: wout_pad [1024,128] bf16 (row 64 h + j <- row 8 h + j), bout_pad [1024], wl_pad [64,128] bf16, bl_pad [64].
+    The pad rows are the caller's zeros and stay untouched."""
+    _chk(wo, bo, wl, bl, wout_pad, bout_pad, wl_pad, bl_pad)
+    T = wl.shape[0]
+    assert 0 < T <= 64, "nms_logit has %d rows, the padded operand 64" % T
+    for t, shape, dt in ((wo, (128, 128), torch.bfloat16), (bo, (128,), torch.float32), (wl, (T, 128), torch.bfloat16), (bl, (T,), torch.float32),
+                         (wout_pad, (1024, 128), torch.bfloat16), (bout_pad, (1024,), torch.float32), (wl_pad, (64, 128), torch.bfloat16),
+                         (bl_pad, (64,), torch.float32)):
+        _dense(t, shape, dt)
+    _lib.call('relnet_lnms_pad_params', wo.data_ptr(), bo.data_ptr(), wl.data_ptr(), bl.data_ptr(), wout_pad.data_ptr(), bout_pad.data_ptr(),
+              wl_pad.data_ptr(), bl_pad.data_ptr(), T, _stream())
+
+
+def lnms_gather_bias(img, rank_idx):
+    """The geometry bias ln G of the class-batched relation module from ONE per-image table: img [B,16,N,Npad] fp32 (geometry_bias of the
+    image's boxes), rank_idx [B,C,F] int32 (>= 0, F <= 512, F <= N) -> out [B*C,16,F,pad32(F)] fp32 with
+    out[b C + c, h, f1, f2] = img[b, h, rank_idx[b,c,f1], rank_idx[b,c,f2]] for f2 < F (pad columns unwritten)."""
+    _chk(img, rank_idx)
+    B, C, F = _ranks(rank_idx)
+    N, Npad = img.shape[2], img.shape[3]
+    _dense(img, (B, 16, N, Npad), torch.float32)
+    assert F <= N <= Npad and F <= 512, (F, N, Npad)
+    out = torch.empty((B * C, 16, F, pad32(F)), device=img.device, dtype=torch.float32)
+    _lib.call('relnet_lnms_gather_bias', img.data_ptr(), rank_idx.data_ptr(), out.data_ptr(), B, C, N, Npad, F, out.shape[-1], _stream())
+    return out
+
+
+def lnms_residual_relu(att, x):
+    """out [..,128] = relu(x [..,128] + att [..,1024][.., 64 h + j], j < 8) (bf16; the sum is rounded before the ReLU)."""
+    _chk(att, x)
+    assert x.shape[-1] == 128 and x.numel() > 0
+    _dense(x, x.shape, torch.bfloat16)
+    _dense(att, tuple(x.shape[:-1]) + (1024,), torch.bfloat16)
+    out = torch.empty_like(x)
+    _lib.call('relnet_lnms_residual_relu', att.data_ptr(), x.data_ptr(), out.data_ptr(), x.numel() // 128, _stream())
+    return out
+
+
+def lnms_cond_multi(logit, sorted_score, T):
+    """cond [B,F,C,T] = sigmoid(logit[(b C + c) F + f, t]), multi = sorted_score [B,F,C] x cond.  logit [B*C*F, >= T] fp32 (one free row stride), T <= 8."""
+    _chk(logit, sorted_score)
+    B, F, C = sorted_score.shape
+    T = int(T)
+    _dense(sorted_score, (B, F, C), torch.float32)
+    assert 0 < T <= 8, "T = %d thresholds (T <= 8)" % T
+    assert logit.dtype == torch.float32 and logit.dim() == 2 and logit.shape[0] == B * C * F and logit.shape[1] >= T and logit.stride(1) == 1 \
+        and logit.stride(0) >= logit.shape[1], (logit.shape, logit.stride(), logit.dtype)
+    cond = torch.empty((B, F, C, T), device=logit.device, dtype=torch.float32)
+    multi = torch.empty_like(cond)
+    _lib.call('relnet_lnms_cond_multi', logit.data_ptr(), logit.stride(0), sorted_score.data_ptr(), cond.data_ptr(), multi.data_ptr(), B, C, F, T, _stream())
+    return cond, multi
+
+
+def lnms_cond_bwd(d_multi, cond, sorted_score):
+    """Adjoint of lnms_cond_multi: d_multi, cond [B,F,C,T] fp32 (T <= 8), sorted_score [B,F,C] -> d_sorted [B,F,C] fp32 = sum_t d_multi cond,
+    d_logit [B*C*F,64] bf16 = d_multi score cond (1 - cond) at row (b C + c) F + f, 0 beyond T."""
+    _chk(d_multi, cond, sorted_score)
+    B, F, C, T = cond.shape
+    assert 0 < T <= 8, "T = %d thresholds (T <= 8)" % T
+    _dense(cond, (B, F, C, T), torch.float32)
+    _dense(d_multi, (B, F, C, T), torch.float32)
+    _dense(sorted_score, (B, F, C), torch.float32)
+    d_sorted = torch.empty((B, F, C), device=cond.device, dtype=torch.float32)
+    d_logit = torch.empty((B * C * F, 64), device=cond.device, dtype=torch.bfloat16)
+    _lib.call('relnet_lnms_cond_bwd', d_multi.data_ptr(), cond.data_ptr(), sorted_score.data_ptr(), d_sorted.data_ptr(), d_logit.data_ptr(), B, C, F, T, _stream())
+    return d_sorted, d_logit
+
+
+def lnms_take_bwd(d_x, rank_idx, N):
+    """Adjoint of the take of lnms_embed: d_x [B,C,F,128] bf16, rank_idx [B,C,F] int32 (negative = padding) -> d_emb [B*N,128] bf16, every row
+    written with the fp32 sum of the rows of d_x whose rank names the roi.  C <= 128, F <= N (lnms_take_bwd_ordered takes the rest)."""
+    _chk(d_x, rank_idx)
+    B, C, F = _ranks(rank_idx)
+    _dense(d_x, (B, C, F, 128), torch.bfloat16)
+    assert C <= 128, "%d classes (C <= 128)" % C
+    assert F <= N and F < 32768, (F, N)
+    d_emb = torch.empty((B * N, 128), device=d_x.device, dtype=torch.bfloat16)
+    _lib.call('relnet_lnms_take_bwd', d_x.data_ptr(), rank_idx.data_ptr(), d_emb.data_ptr(), B, N, C, F, _stream())
+    return d_emb
+
+
+def lnms_softmax_bwd(prob, d_prob, d_cls):
+    """Backward of prob = softmax(cls_score)[:, :, 1:] ACCUMULATED into d_cls [B,R,C+1] fp32 (R >= N; rows and images: free strides):
+    d_cls[b,n,0] += -(1 - sum prob) inner, d_cls[b,n,1+c] += prob_c (d_prob_c - inner), inner = sum_c prob_c d_prob_c.  prob, d_prob [B,N,C] fp32."""
+    _chk(prob, d_prob, d_cls)
+    B, N, C = prob.shape
+    _dense(prob, (B, N, C), torch.float32)
+    _dense(d_prob, (B, N, C), torch.float32)
+    assert d_cls.dtype == torch.float32 and d_cls.dim() == 3 and d_cls.shape[0] == B and d_cls.shape[1] >= N and d_cls.shape[2] == C + 1, \
+        (d_cls.shape, d_cls.dtype, prob.shape)
+    assert d_cls.stride(2) == 1 and d_cls.stride(1) >= C + 1 and (B == 1 or d_cls.stride(0) >= d_cls.shape[1] * d_cls.stride(1)), d_cls.stride()
+    _lib.call('relnet_lnms_softmax_bwd', prob.data_ptr(), d_prob.data_ptr(), d_cls.data_ptr(), d_cls.stride(1), d_cls.stride(0), B, N, C, _stream())
 
 
 # ---------------------------------------------------------------------------------------

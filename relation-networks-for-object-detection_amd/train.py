@@ -21,6 +21,8 @@ MI355X-first choices:
     recomputed from their inputs instead of storing [16, N, M] maps.
 """
 
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -29,6 +31,7 @@ from . import dist as D
 from .backbone import unit_names, conv_bn_names, fold_bn, EPS
 from .relation import attention_module_backward, _module_forward, pack_pair_pos, GradSink
 from .detector import Config, fc1_channels_last_perm
+from .learn_nms import LearnNMSTrain, rank_embedding
 from .pooling import RoiPooling
 from .operator_py.proposal import generate_anchors, propose_batch
 
@@ -308,8 +311,8 @@ class Trainer(object):
             biases.append(('nms_qk_1', torch.cat([params['nms_query_1_bias'], params['nms_key_1_bias']], 0)))
             weights.append(('nms_linear_out_1', params['nms_linear_out_1_weight'].reshape(128, 128)))
             biases.append(('nms_linear_out_1', params['nms_linear_out_1_bias']))
-            from .learn_nms import rank_embedding
             self.rank_emb = rank_embedding(c.first_n, 1024).to(dev, torch.bfloat16).contiguous()
+            self._lnms = LearnNMSTrain(self)
         self.lr_mult_tail = None
         if c.dcn:           # `offset` FC has lr_mult = 0.01 (SYM_DCN_RELNMS:1075): keep it LAST so it is one tail range
             weights.append(('offset', params['offset_weight'][:, self.fc1_perm])); biases.append(('offset', params['offset_bias']))
@@ -854,179 +857,8 @@ class Trainer(object):
         return d_pool, (x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem)
 
     def _lnms_forward_backward(self, cls_score, bbox_pred, rois, im_info, feat, gt_boxes, num_gt, n_valid=None, d_cls_out=None):
-        """Train branch of the learn-NMS head (symbols/..._learn_nms.py:424-551) and its adjoint.
-        cls_score [B,N,81] fp32, bbox_pred [B,N,8] ([B,N,4*81] class-specific: learn_nms.py:283-287,311-321) (BlockGrad), rois [B,N,5], feat = fc_all_2_relu[:, :N] bf16.
-        Returns (d cls_score [B,N,81] fp32, d feat [B,N,1024] (bf16, as the projection's backward GEMM leaves it), losses); with d_cls_out [B,R,81] fp32 (contiguous, R >= N) the
-        class-score gradient is accumulated into d_cls_out[:, :N] instead and None is returned in its place.
-        cfg.lnms_fused_glue (default on; off = the tensor-operator chains of rounds 3 - 5, kept for the equality test):
-        the element-wise chains of the branch run as single kernels (csrc/lnms_train.hip)."""
-        import ctypes
-        from . import lib as _lib
-        c = self.cfg
-        fused = bool(getattr(c, 'lnms_fused_glue', True))
-        B, N, C1 = cls_score.shape
-        C, F, Tn = C1 - 1, c.first_n, len(c.nms_target_thresh)
-        dev, bt, s_ = cls_score.device, torch.bfloat16, ops._stream()
-        cs, bp_ = cls_score.contiguous().view(B * N, C1), bbox_pred.contiguous().view(B * N, -1)
-        prob = torch.empty((B, N, C), device=dev, dtype=torch.float32)
-        means, stds = (ctypes.c_float * 4)(*c.bbox_means), (ctypes.c_float * 4)(*c.bbox_stds)
-        if self.class_agnostic:
-            boxes = torch.empty((B, N, 4), device=dev, dtype=torch.float32)
-            _lib.call('relnet_lnms_prepare_ex', cs.data_ptr(), cs.stride(0), bp_.data_ptr(), bp_.stride(0), rois.data_ptr(),
-                      im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, 4, means, stds, ops._ptr(n_valid), s_)
-        else:       # every foreground class refined from its own four columns
-            assert bp_.shape[1] == 4 * C1, bp_.shape
-            boxes = torch.empty((B, N, C, 4), device=dev, dtype=torch.float32)
-            _lib.call('relnet_lnms_prepare_cs', cs.data_ptr(), cs.stride(0), bp_.data_ptr(), bp_.stride(0), rois.data_ptr(),
-                      im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1, means, stds, ops._ptr(n_valid), s_)
-        rank_idx = torch.empty((B, C, F), device=dev, dtype=torch.int32)
-        sorted_score = torch.empty((B, F, C), device=dev, dtype=torch.float32)
-        sorted_bbox = torch.empty((B, F, C, 4), device=dev, dtype=torch.float32)
-        class_boxes = torch.empty((B, C, F, 4), device=dev, dtype=torch.float32)
-        class_max = torch.empty((B, C), device=dev, dtype=torch.float32)
-        _lib.call('relnet_lnms_sort' if self.class_agnostic else 'relnet_lnms_sort_cs', prob.data_ptr(), boxes.data_ptr(), rank_idx.data_ptr(),
-                  sorted_score.data_ptr(), sorted_bbox.data_ptr(), class_boxes.data_ptr(), class_max.data_ptr(), B, N, C, F, s_)
-        rank_feat = ops.gemm_nt(self.rank_emb, self.w('nms_rank'), self.b('nms_rank'), out_dtype=torch.float32)      # [F,128]
-        feat2 = feat.contiguous().view(B * N, -1)
-        roi_emb = ops.gemm_nt(feat2, self.w('roi_feat_embedding'), self.b('roi_feat_embedding'))
-        x = torch.empty((B, C, F, 128), device=dev, dtype=bt)
-        _lib.call('relnet_lnms_embed', roi_emb.data_ptr(), rank_feat.data_ptr(), rank_idx.data_ptr(), x.data_ptr(),
-                  B, N, C, F, 128, ops._dt(x), s_)
-        BC = B * C
-        xr = x.view(BC, F, 128)
-        # relation module over (image, class): 16 heads x 64 for Q/K, each head's 8 output channels padded to a 64-wide tile
-        class M_(object):
-            pass
-        mod = M_()
-        mod.wqk, mod.bqk = self.w('nms_qk_1'), self.b('nms_qk_1')
-        wo, bo = self.w('nms_linear_out_1'), self.b('nms_linear_out_1')
-        mod.wout = self._scratch('nms_wout_pad', (1024, 128), bt)           # persistent: the 56 pad rows of every head stay zero
-        mod.bout = self._scratch('nms_bout_pad', (1024,), torch.float32)
-        if fused:       # the four padded operands of the step (Wout / bout per head, the 64-row logit matrix) refreshed by one launch
-            w_logit, b_logit = self._scratch('nms_wlogit_pad', (64, 128), bt), self._scratch('nms_blogit_pad', (64,), torch.float32)
-            _lib.call('relnet_lnms_pad_params', wo.data_ptr(), bo.data_ptr(), self.w('nms_logit').data_ptr(), self.b('nms_logit').data_ptr(),
-                      mod.wout.data_ptr(), mod.bout.data_ptr(), w_logit.data_ptr(), b_logit.data_ptr(), Tn, s_)
-        else:
-            mod.wout.view(16, 64, 128)[:, :8] = wo.view(16, 8, 128)
-            mod.bout.view(16, 64)[:, :8] = bo.view(16, 8)
-        mod.wp = self.W.view(self.W.master, 'nms_pair_pos_fc1_1')
-        mod.bp = self.b('nms_pair_pos_fc1_1')
-        wp_t, bp = pack_pair_pos([mod], dev)
-        cb = class_boxes.view(BC, F, 4)
-        if fused and n_valid is None and self.class_agnostic:
-            # ln G once per IMAGE (B N^2 pairs instead of B C F^2: 9 x fewer at 300 rois / 80 classes / first_n 100), then gathered per class by its ranks
-            # (relnet_lnms_gather_bias): the class's boxes are the image's boxes re-ordered, same arithmetic on the same pairs -> bit-identical
-            assert boxes.shape == (B, N, 4), "the per-image shortcut needs ONE box per roi (class-agnostic regression)"
-            img = ops.geometry_bias(boxes, wp_t, bp, N, fast32=True)[0]                    # [B,16,N,Npad]
-            bias = torch.empty((BC, 16, F, ops.pad32(F)), device=dev, dtype=torch.float32)
-            _lib.call('relnet_lnms_gather_bias', img.data_ptr(), rank_idx.data_ptr(), bias.data_ptr(), B, C, N, img.shape[-1], F, bias.shape[-1], s_)
-        else:       # (class-specific boxes: a class's boxes are NOT the image's boxes re-ordered, every class has its own N -- the shortcut's premise is false)
-            bias = ops.geometry_bias(cb, wp_t, bp, F, fast32=True)[0]
-        lcache = {}
-        att, _, _ = _module_forward(xr, mod, bias, F, True, False, False, vwt_buf=self._scratch('vwt_nms_%d' % F, (BC, 1024, bias.shape[-1]), bt),
-                                    cache=lcache)                                               # [BC,F,1024]
-        if fused:
-            assert att.is_contiguous() and att.shape == (BC, F, 1024) and att.dtype == bt and xr.is_contiguous()
-            allf = torch.empty((BC, F, 128), device=dev, dtype=bt)
-            _lib.call('relnet_lnms_residual_relu', att.data_ptr(), xr.data_ptr(), allf.data_ptr(), BC * F, s_)
-            logit64 = ops.gemm_nt(allf.view(BC * F, 128), w_logit, b_logit, out_dtype=torch.float32)      # [BC*F, 64], T real columns
-            cond = torch.empty((B, F, C, Tn), device=dev, dtype=torch.float32)
-            multi = torch.empty_like(cond)
-            _lib.call('relnet_lnms_cond_multi', logit64.data_ptr(), logit64.stride(0), sorted_score.data_ptr(), cond.data_ptr(), multi.data_ptr(),
-                      B, C, F, Tn, s_)
-        else:
-            att128 = att.view(BC, F, 16, 64)[..., :8].reshape(BC, F, 128)
-            allf = torch.relu(xr + att128).contiguous()
-            w_logit = torch.zeros((64, 128), device=dev, dtype=bt); w_logit[:Tn] = self.w('nms_logit')
-            b_logit = torch.zeros(64, device=dev, dtype=torch.float32); b_logit[:Tn] = self.b('nms_logit')
-            logit = ops.gemm_nt(allf.view(BC * F, 128), w_logit, b_logit, out_dtype=torch.float32)[:, :Tn]
-            cond = torch.sigmoid(logit).view(B, C, F, Tn).permute(0, 2, 1, 3).contiguous()          # [B,F,C,T]
-            multi = sorted_score.unsqueeze(3) * cond
-        target = ops.nms_multi_target(sorted_bbox, gt_boxes, sorted_score, num_gt, c.nms_target_thresh)
-        pos, neg, d_multi = losses.nms_loss(multi, target, F, Tn, c.nms_loss_scale, c.nms_pos_scale, c.nms_eps)
-        det = self.deterministic
-        lo = dict(nms_pos_loss=T.scalar_sum(pos, 1.0 / B, deterministic=det), nms_neg_loss=T.scalar_sum(neg, 1.0 / B, deterministic=det), nms_multi_score=multi, nms_multi_target=target,
-                  sorted_score=sorted_score, nms_rank_idx=rank_idx, nms_class_boxes=class_boxes)
-        if self.metrics is not None:        # NMSLoss_pos / _neg (B images: one image = one executor in the reference), NMSAcc_pos / _neg
-            self.metrics.add_nms(target, cond, pos, neg, B)
-            lo.update(nms_conditional_score=cond, nms_pos_loss_map=pos, nms_neg_loss_map=neg)
-        # ---------------- adjoint ----------------
-        if fused:
-            d_sorted = torch.empty((B, F, C), device=dev, dtype=torch.float32)
-            d_logit_p = torch.empty((BC * F, 64), device=dev, dtype=bt)
-            _lib.call('relnet_lnms_cond_bwd', d_multi.data_ptr(), cond.data_ptr(), sorted_score.data_ptr(), d_sorted.data_ptr(), d_logit_p.data_ptr(),
-                      B, C, F, Tn, s_)
-        else:
-            d_sorted = (d_multi * cond).sum(3)                                                      # [B,F,C]
-            d_logit = (d_multi * sorted_score.unsqueeze(3) * cond * (1.0 - cond)).permute(0, 2, 1, 3).reshape(BC * F, Tn)
-            d_logit_p = torch.zeros((BC * F, 64), device=dev, dtype=bt); d_logit_p[:, :Tn] = d_logit
-        wl_t = self.wt('nms_logit')
-        if fused and wl_t is not None:
-            # logit layer backward on the step's own machinery: W^T from the relayout table, the weight gradient in the bucket's grouped launch
-            # (Tn real of 64 padded output columns), the bias gradient in its grouped column sum (was 8 library launches: transpose, fills, casts, sums)
-            d_allf = ops.gemm_nt(d_logit_p, wl_t)
-            T._wg_call(self._wg('nms_logit'), d_logit_p, allf.view(BC * F, 128), cout=Tn)
-            T.colsum_add(d_logit_p[:, :Tn], *self._bg('nms_logit'))
-        else:
-            d_allf, dw, db = T.linear_bwd(allf.view(BC * F, 128), w_logit, d_logit_p, w_t=None, keep_splits=True)
-            self._add_wgrad('nms_logit', dw.sum(0)[:Tn]); self._add_bgrad('nms_logit', db[:Tn])
-        g = T.relu_bwd(d_allf, allf.view(BC * F, 128))                                          # [BC*F,128] bf16
-        dY = self._scratch('nms_dy_pad', (BC, F, 1024), bt)                   # persistent: columns 8 .. 63 of every head stay zero
-        dY.view(BC, F, 16, 64)[..., :8] = g.view(BC, F, 16, 8)
-        # gradients through relation.GradSink: [dQ | dK | dVW] packed once, ONE projection-backward GEMM (K = 3072) with the residual
-        # gradient g in its epilogue; the [Wq; Wk] product goes straight into the flat buffer, the padded Wout product through a
-        # [1024, 128] scratch whose 8 real rows per head are then added to the compact [128, 128] gradient
-        wcat_t = self._relayout.get('rel_cat_nms')
-        assert wcat_t is not None
-        gq = self.W.view(self.W.grad, 'nms_qk_1')
-        glo = self._scratch('nms_dwout_pad', (1024, 128), torch.float32)
-        glo.zero_()
-
-        def wg(dy2d, x2d):
-            ops.wgrad_tn(dy2d[:, :2048], x2d, out=gq.view(2048, 128), deterministic=det)
-            ops.wgrad_tn(dy2d[:, 2048:], x2d, out=glo, deterministic=det)
-        sink = GradSink(wcat_t, g.view(BC, F, 128), wg, self._bg('nms_qk_1'), None,
-                        self.W.view(self.W.grad, 'nms_pair_pos_fc1_1'), self.Bv.view(self.Bv.grad, 'nms_pair_pos_fc1_1'), self._scratch, deterministic=det)
-        r = attention_module_backward(xr, cb, None, dY, nongt_dim=F, index=1, dtype=bt, packed=mod, cache=lcache, sink=sink)
-        self.W.view(self.W.grad, 'nms_linear_out_1').view(16, 8, 128).add_(glo.view(16, 64, 128)[:, :8])
-        T.colsum_add(g.view(BC * F, 128), *self._bg('nms_linear_out_1'))    # (dY's real columns are g's columns)
-        d_x = r['d_roi_feat'].view(B, C, F, 128)                            # bf16: residual + module
-        if fused and d_x.is_contiguous():
-            d_rank = torch.zeros((F, 128), device=dev, dtype=torch.float32)                     # sum over (image, class): one column-sum launch (fp32 accumulation)
-            if det:
-                T.colsum_add(d_x.view(BC, F * 128), d_rank.view(-1), deterministic=True)
-            else:
-                _lib.call('relnet_colsum_add', d_x.data_ptr(), F * 128, BC, F * 128, ops._dt(d_x), d_rank.data_ptr(), s_)
-            T._wg_call(self._wg('nms_rank'), d_rank.to(bt), self.rank_emb)
-            T.colsum_add(d_rank, *self._bg('nms_rank'))
-        else:
-            d_rank = d_x.sum((0, 1), dtype=torch.float32)                                       # [F,128] (fp32 accumulation whatever d_x's dtype)
-            self._add_wgrad('nms_rank', T.wgrad(d_rank.to(bt), self.rank_emb)); self._add_bgrad('nms_rank', d_rank.sum(0))
-        if fused and d_x.dtype == bt and d_x.is_contiguous() and C <= 128:
-            d_emb = torch.empty((B * N, 128), device=dev, dtype=bt)          # every row written: gathered per roi over the classes that rank it (fp32 sums)
-            _lib.call('relnet_lnms_take_bwd', d_x.data_ptr(), rank_idx.data_ptr(), d_emb.data_ptr(), B, N, C, F, s_)
-        elif det and d_x.is_contiguous() and d_x.dtype in (bt, torch.float32):
-            # the ordered gather for the operands the kernel above does not take (no index_add_: torch's scatter adds with float atomics)
-            d_emb = ops.lnms_take_bwd_ordered(d_x, rank_idx, N).to(bt)
-        else:
-            if det:
-                raise ValueError("deterministic training: the learn-NMS take adjoint needs a contiguous bf16 / fp32 gradient (index_add_ uses float atomics)")
-            d_emb = torch.zeros((B * N, 128), device=dev, dtype=torch.float32)
-            flat = (rank_idx.long() + (torch.arange(B, device=dev) * N).view(B, 1, 1)).view(-1)
-            d_emb.index_add_(0, flat, d_x.reshape(-1, 128).float())                             # take() backward (a roi is ranked in up to 80 classes: fp32 sums)
-            d_emb = d_emb.to(bt)
-        d_feat, dw, db = T.linear_bwd(feat2, self.w('roi_feat_embedding'), d_emb, w_t=self.wt('roi_feat_embedding'), keep_splits=True, wgrad_to=self._wg('roi_feat_embedding'), bgrad_to=self._bg('roi_feat_embedding'))
-        self._add_bgrad('roi_feat_embedding', db)
-        # sort / slice backward -> cls_prob -> softmax backward (background column has no direct gradient)
-        d_prob = ops.lnms_scatter_bwd(d_sorted.contiguous(), rank_idx, N)      # d_prob[b, rank_idx[b,c,f], c] += d_sorted[b,f,c]
-        if fused and d_cls_out is not None and d_cls_out.is_contiguous() and d_cls_out.dtype == torch.float32 and d_cls_out.shape[2] == C1:
-            _lib.call('relnet_lnms_softmax_bwd', prob.data_ptr(), d_prob.data_ptr(), d_cls_out.data_ptr(), d_cls_out.stride(1), d_cls_out.stride(0),
-                      B, N, C, s_)
-            return None, d_feat.view(B, N, -1), lo
-        p_bg = 1.0 - prob.sum(2, keepdim=True)
-        inner = (prob * d_prob).sum(2, keepdim=True)
-        d_cls = torch.cat([-p_bg * inner, prob * (d_prob - inner)], 2)
-        return d_cls, d_feat.view(B, N, -1), lo
+        """Train branch of the learn-NMS head and its adjoint: learn_nms.LearnNMSTrain.__call__ (arguments and return values there)."""
+        return self._lnms(cls_score, bbox_pred, rois, im_info, feat, gt_boxes, num_gt, n_valid=n_valid, d_cls_out=d_cls_out)
 
     def _dgrad_w(self, name, cout):
         """[Cout, 9*Cin] packed forward weights -> [Cin, 9*Cout] tap-flipped data-gradient weights."""
@@ -1038,15 +870,9 @@ class Trainer(object):
         return w.view(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).reshape(cin, 9 * cout).contiguous()
 
     def _rel_params(self, i):
-        class P(object):
-            pass
-        m = P()
-        m.wqk, m.bqk = self.w('qk_%d' % i), self.b('qk_%d' % i)
-        m.wout, m.bout = self.w('linear_out_%d' % i), self.b('linear_out_%d' % i)
-        m.wqk_t, m.wout_t = self.wt('qk_%d' % i), self.wt('linear_out_%d' % i)
-        m.wp = self.W.view(self.W.master, 'pair_pos_fc1_%d' % i)
-        m.bp = self.b('pair_pos_fc1_%d' % i)
-        return m
+        return SimpleNamespace(wqk=self.w('qk_%d' % i), bqk=self.b('qk_%d' % i), wout=self.w('linear_out_%d' % i), bout=self.b('linear_out_%d' % i),
+                               wqk_t=self.wt('qk_%d' % i), wout_t=self.wt('linear_out_%d' % i),
+                               wp=self.W.view(self.W.master, 'pair_pos_fc1_%d' % i), bp=self.b('pair_pos_fc1_%d' % i))
 
     def _relation_bwd(self, i, mod, f, x_act, rois, d_x, N, key_count=None, cache=None):
         """x_act = relu(f + relation_i(f)); returns d f (bf16, residual path + module path) and accumulates the module's parameter

@@ -61,6 +61,21 @@ def test_product_does_not_import_oracle():
                 assert 'import oracle' not in src and 'from oracle' not in src, f
 
 
+def test_model_code_reaches_the_kernels_through_front_ends_only():
+    """train.py, learn_nms.py, detector.py, relation.py and pooling.py hold no raw C-ABI call and turn no tensor into a pointer: pointers and
+    strides are made in the checked front ends (ops.py, train_ops.py, losses.py) alone."""
+    import ast
+    pkg_dir = os.path.join(ROOT, 'relation-networks-for-object-detection_amd')
+    for f in ('train.py', 'learn_nms.py', 'detector.py', 'relation.py', 'pooling.py'):
+        bad = []
+        for node in ast.walk(ast.parse(open(os.path.join(pkg_dir, f)).read(), f)):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute):
+                fn = node.func
+                if fn.attr == 'data_ptr' or (fn.attr == 'call' and isinstance(fn.value, ast.Name) and fn.value.id in ('lib', '_lib')):
+                    bad.append('%s:%d .%s()' % (f, node.lineno, fn.attr))
+        assert not bad, bad
+
+
 def test_proposal_prop_protocol():
     import relnet_amd  # noqa: F401
     from relnet_amd import operator_py

@@ -218,29 +218,13 @@ def test_learn_nms_class_specific_matches_reference_operator(rn, gold, name):
 
 
 def _prepare_sort(rn, cls_score, bbox_pred, rois, im_info, first_n, class_agnostic, n_valid=None, norm=None):
-    """relnet_lnms_prepare* + relnet_lnms_sort* as LearnNMS.forward calls them -> prob, boxes, rank_idx, sorted_score, sorted_bbox,
-    class_boxes, class_max."""
-    import ctypes
-    ops, call = rn.ops, rn.lib.call
+    """learn_nms.rank_stage (relnet_lnms_prepare* + relnet_lnms_sort*, what LearnNMS.forward and the train branch call) into poisoned prob / boxes
+    -> prob, boxes, rank_idx, sorted_score, sorted_bbox, class_boxes, class_max."""
     B, N, C1 = cls_score.shape
-    C, F = C1 - 1, first_n
-    dev, f32 = cls_score.device, torch.float32
-    cs, bp = cls_score.reshape(B * N, C1), bbox_pred.reshape(B * N, -1)
-    means = None if norm is None else (ctypes.c_float * 4)(*norm[0])
-    stds = None if norm is None else (ctypes.c_float * 4)(*norm[1])
-    prob = torch.full((B, N, C), -1.0, device=dev, dtype=f32)
-    boxes = torch.full((B, N, 4) if class_agnostic else (B, N, C, 4), -1.0, device=dev, dtype=f32)
-    head = (cs.data_ptr(), cs.stride(0), bp.data_ptr(), bp.stride(0), rois.data_ptr(), im_info.data_ptr(), prob.data_ptr(), boxes.data_ptr(), B, N, C1)
-    if class_agnostic:
-        call('relnet_lnms_prepare_ex', *head, 4, means, stds, ops._ptr(n_valid), ops._stream())
-    else:
-        call('relnet_lnms_prepare_cs', *head, means, stds, ops._ptr(n_valid), ops._stream())
-    rank_idx = torch.empty((B, C, F), device=dev, dtype=torch.int32)
-    sorted_score, sorted_bbox = torch.empty((B, F, C), device=dev, dtype=f32), torch.empty((B, F, C, 4), device=dev, dtype=f32)
-    class_boxes, class_max = torch.empty((B, C, F, 4), device=dev, dtype=f32), torch.empty((B, C), device=dev, dtype=f32)
-    call('relnet_lnms_sort' if class_agnostic else 'relnet_lnms_sort_cs', prob.data_ptr(), boxes.data_ptr(), rank_idx.data_ptr(),
-         sorted_score.data_ptr(), sorted_bbox.data_ptr(), class_boxes.data_ptr(), class_max.data_ptr(), B, N, C, F, ops._stream())
-    return prob, boxes, rank_idx, sorted_score, sorted_bbox, class_boxes, class_max
+    prob = torch.full((B, N, C1 - 1), -1.0, device=cls_score.device, dtype=torch.float32)
+    boxes = torch.full((B, N, 4) if class_agnostic else (B, N, C1 - 1, 4), -1.0, device=cls_score.device, dtype=torch.float32)
+    means, stds = norm if norm else (None, None)
+    return rn.learn_nms.rank_stage(cls_score, bbox_pred, rois, im_info, first_n, class_agnostic, means, stds, n_valid, out=(prob, boxes))
 
 
 @pytest.mark.parametrize('name', ['cs_n60_c6_f20_norm', 'cs_n120_c80_f30'])
