@@ -115,7 +115,7 @@ class LearnNMS(object):
 
 class LearnNMSTrain(object):
     """Train branch of the learn-NMS head (symbols/..._learn_nms.py:424-551) and its adjoint, on a Trainer's parameters.  The trainer owns the
-    parameters, their relayout entries and the gradient buffers; this class reaches them as Trainer._relation_bwd does: w / b / wt, _wg / _bg
+    parameters, their relayout entries and the gradient buffers; this class reaches them as relation.BoxHeadTrain does: w / b / wt, _wg / _bg
     (and _add_wgrad / _add_bgrad for the tensor-operator form), _scratch, the W / Bv gradient views, _relayout.get, deterministic, metrics.
 
     The element-wise chains of the branch exist in two forms, chosen once per direction by cfg.lnms_fused_glue: single kernels

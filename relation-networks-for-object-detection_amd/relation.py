@@ -9,9 +9,11 @@ group, index)` (:85-151) and the fc_new_1 -> relation -> fc_new_2 -> relation ->
 boxes directly, so `position_embedding` is replaced by the rois themselves.
 """
 
+from types import SimpleNamespace
+
 import torch
 
-from . import ops
+from . import ops, train_ops as _T
 
 
 class RelationParams(object):
@@ -110,9 +112,49 @@ def _module_forward(f, mod, bias, M, want_out, want_act, want_logits, vwt_buf=No
     return r
 
 
-class RelationHead(object):
-    """fc_new_1 -> relation_1 -> ReLU -> fc_new_2 -> relation_2 -> ReLU -> cls_score / bbox_pred
-    (SYM_REL:254-280).  `dtype` bf16 is the throughput path, float32 the parity path."""
+class BoxHead(object):
+    """The one forward of the box head, fc_new_1 -> relation_1 -> ReLU -> fc_new_2 -> relation_2 -> ReLU -> cls_score | bbox_pred
+    (SYM_REL:254-280), or the plain 2FC head (resnet_v1_101_rcnn.py:125-134) when `mods` is None, on packed tensors that it does not
+    own: RelationHead packs them from a parameter dict, BoxHeadTrain hands in views of a trainer's flat buffers.
+    w1 [1024, 12544], w2 [1024, 1024], wcb [C + 4 num_reg, 1024] = [cls_score; bbox_pred] (b* fp32); mods: two namespaces with
+    wqk, bqk, wout, bout, wp, bp (RelationParams)."""
+
+    def __init__(self, w1, b1, w2, b2, wcb, bcb, num_classes, mods=None):
+        self.w1, self.b1, self.w2, self.b2, self.wcb, self.bcb = w1, b1, w2, b2, wcb, bcb
+        self.num_classes, self.mods = int(num_classes), mods
+        self._vwt = {}
+
+    def _vwt_buf(self, i, f, Mpad, M):
+        """Persistent VW^T buffer of module i: the GEMM only writes [:, :, :M], the pad columns stay zero from call to call (no per-step
+        fill).  Keyed on M too: a smaller M in the same padded width would inherit stale columns [M, Mpad)."""
+        key = (i, f.shape[0], Mpad, M)
+        if key not in self._vwt:
+            self._vwt[key] = torch.zeros((f.shape[0], self.mods[i].wout.shape[0], Mpad), device=f.device, dtype=f.dtype)
+        return self._vwt[key]
+
+    def run(self, pooled2, B, M=None, bias=(None, None), rois=None, key_count=None, want_y=False, caches=(None, None)):
+        """pooled2 [B*N, 12544] -> namespace f1, y1, x1, f2, y2, x2 [B,N,1024], cls_score [B,N,C], bbox_pred (fp32 column slices of one
+        GEMM's output).  The first M rows of each image are the keys of both modules; bias [2,B,16,N,Mpad] is the caller's geometry
+        (fp16 log2 at inference, float32 ln in training; (None, None) + rois: evaluated inside the fused attention kernel);
+        want_y: the module outputs y_i (None otherwise); caches: the per-module dicts of _module_forward.  Plain head: f_i = x_i."""
+        N = pooled2.shape[0] // B
+        s = SimpleNamespace(y1=None, y2=None)
+        if self.mods is None:       # fc + ReLU in the GEMM epilogue
+            s.f1 = s.x1 = ops.gemm_nt(pooled2, self.w1, self.b1, relu=True).reshape(B, N, -1)
+            s.f2 = s.x2 = ops.gemm_nt(s.x1.reshape(B * N, -1), self.w2, self.b2, relu=True).reshape(B, N, -1)
+        else:
+            Mpad = ops.pad32(M) if bias[0] is None else bias[0].shape[-1]
+            s.f1 = ops.gemm_nt(pooled2, self.w1, self.b1).reshape(B, N, -1)
+            s.y1, s.x1, _ = _module_forward(s.f1, self.mods[0], bias[0], M, want_y, True, False, self._vwt_buf(0, s.f1, Mpad, M), rois, key_count, caches[0])
+            s.f2 = ops.gemm_nt(s.x1.reshape(B * N, -1), self.w2, self.b2).reshape(B, N, -1)
+            s.y2, s.x2, _ = _module_forward(s.f2, self.mods[1], bias[1], M, want_y, True, False, self._vwt_buf(1, s.f2, Mpad, M), rois, key_count, caches[1])
+        cb = ops.gemm_nt(s.x2.reshape(B * N, -1), self.wcb, self.bcb, out_dtype=torch.float32).reshape(B, N, -1)
+        s.cls_score, s.bbox_pred = cb[:, :, :self.num_classes], cb[:, :, self.num_classes:]
+        return s
+
+
+class RelationHead(BoxHead):
+    """The box head of the test graphs, packed once from a parameter dict.  `dtype` bf16 is the throughput path, float32 the parity path."""
 
     def __init__(self, params, dtype=torch.bfloat16, device='cuda', fc1_perm=None, use_relation=True,
                  fc_names=('fc_new_1', 'fc_new_2'), fused=False):
@@ -122,53 +164,35 @@ class RelationHead(object):
         w1 = torch.as_tensor(params[n1 + '_weight'])
         if fc1_perm is not None:            # (C,7,7) -> (7,7,C) input order for channels-last pooling
             w1 = w1[:, fc1_perm]
-        self.w1, self.b1 = t(w1, dtype), t(params[n1 + '_bias'], torch.float32)
-        self.w2, self.b2 = t(params[n2 + '_weight'], dtype), t(params[n2 + '_bias'], torch.float32)
         wcb = torch.cat([torch.as_tensor(params['cls_score_weight']), torch.as_tensor(params['bbox_pred_weight'])], 0)
         bcb = torch.cat([torch.as_tensor(params['cls_score_bias']), torch.as_tensor(params['bbox_pred_bias'])], 0)
-        self.num_classes = int(params['cls_score_weight'].shape[0])
-        self.wcb, self.bcb = t(wcb, dtype), t(bcb, torch.float32)
         self.use_relation = use_relation
         # fused: one geometry + attention kernel per module, no bias tensor in HBM -- built and parity-tested, but at B = 54
         # it is slower (272 us / module) than the matrix-core geometry kernel + LDS attention kernel
         self.fused = fused
+        BoxHead.__init__(self, t(w1, dtype), t(params[n1 + '_bias'], torch.float32), t(params[n2 + '_weight'], dtype), t(params[n2 + '_bias'], torch.float32),
+                         t(wcb, dtype), t(bcb, torch.float32), params['cls_score_weight'].shape[0],
+                         [RelationParams(params, i, dtype, device) for i in (1, 2)] if use_relation else None)
         if use_relation:
-            self.mods = [RelationParams(params, i, dtype, device) for i in (1, 2)]
             self.wp_t, self.bp = pack_pair_pos(self.mods, device)
-        self._vwt = {}
 
-    def _vwt_buf(self, B, Mpad, M):
-        key = (B, Mpad, M)            # keyed on M too: a smaller M in the same padded width would inherit stale columns [M, Mpad)
-        if key not in self._vwt:      # pad columns stay zero: the GEMM only writes [:, :, :M]
-            self._vwt[key] = [torch.zeros((B, 1024, Mpad), device=self.device, dtype=self.dtype) for _ in range(2)]
-        return self._vwt[key]
-
-    def forward(self, pooled, rois, nongt_dim=None, return_intermediates=False, key_count=None):
+    def forward(self, pooled, rois, nongt_dim=None, return_intermediates=False, key_count=None, bias=None):
         """pooled [B, N, 12544] (dtype), rois [B, N, 5] fp32 -> cls_score [B,N,C], bbox_pred [B,N,8]
         (fp32 logits; softmax / decoding live in postprocess).  key_count [B] int32: real rows per image when the roi
-        buffer is padded to a fixed size (FPN dummy rois, truncated proposal lists); padded rows are no relation keys."""
+        buffer is padded to a fixed size (FPN dummy rois, truncated proposal lists); padded rows are no relation keys.
+        bias [2,B,16,N,Mpad] (optional): the geometry of both modules from the caller instead of this head's own."""
         B, N, K = pooled.shape
-        if not self.use_relation:        # plain 2FC head, resnet_v1_101_rcnn.py:125-134
-            x1 = ops.gemm_nt(pooled.reshape(B * N, K), self.w1, self.b1, relu=True)
-            x2 = ops.gemm_nt(x1, self.w2, self.b2, relu=True).reshape(B, N, -1)
-            cb = ops.gemm_nt(x2.reshape(B * N, -1), self.wcb, self.bcb, out_dtype=torch.float32).reshape(B, N, -1)
-            return cb[:, :, :self.num_classes], cb[:, :, self.num_classes:], x2
         M = N if nongt_dim is None else nongt_dim
-        if self.fused and fused_ok(self.dtype, M) and key_count is None:
-            bias = (None, None)                 # geometry evaluated inside the attention kernel of each module
-        else:
-            bias = ops.geometry_bias(rois, self.wp_t, self.bp, M, half=self.dtype == torch.bfloat16)   # [2,B,16,N,Mpad]
-        vw = self._vwt_buf(B, ops.pad32(M), M)
-        f1 = ops.gemm_nt(pooled.reshape(B * N, K), self.w1, self.b1).reshape(B, N, -1)
-        y1, x1, _ = _module_forward(f1, self.mods[0], bias[0], M, return_intermediates, True, False, vw[0], rois, key_count)
-        f2 = ops.gemm_nt(x1.reshape(B * N, -1), self.w2, self.b2).reshape(B, N, -1)
-        y2, x2, _ = _module_forward(f2, self.mods[1], bias[1], M, return_intermediates, True, False, vw[1], rois, key_count)
-        cb = ops.gemm_nt(x2.reshape(B * N, -1), self.wcb, self.bcb, out_dtype=torch.float32).reshape(B, N, -1)
-        cls_score, bbox_pred = cb[:, :, :self.num_classes], cb[:, :, self.num_classes:]
-        if return_intermediates:
-            return dict(fc_new_1=f1, attention_1=y1, fc_all_1_relu=x1, fc_new_2=f2, attention_2=y2,
-                        fc_all_2_relu=x2, cls_score=cls_score, bbox_pred=bbox_pred)
-        return cls_score, bbox_pred, x2
+        if self.use_relation and bias is None:
+            if self.fused and fused_ok(self.dtype, M) and key_count is None:
+                bias = (None, None)             # geometry evaluated inside the attention kernel of each module
+            else:
+                bias = ops.geometry_bias(rois, self.wp_t, self.bp, M, half=self.dtype == torch.bfloat16)   # [2,B,16,N,Mpad]
+        s = self.run(pooled.reshape(B * N, K), B, M, bias, rois, key_count, want_y=return_intermediates)
+        if return_intermediates and self.use_relation:
+            return dict(fc_new_1=s.f1, attention_1=s.y1, fc_all_1_relu=s.x1, fc_new_2=s.f2, attention_2=s.y2,
+                        fc_all_2_relu=s.x2, cls_score=s.cls_score, bbox_pred=s.bbox_pred)
+        return s.cls_score, s.bbox_pred, s.x2
 
 
 class GradSink(object):
@@ -275,7 +299,6 @@ def attention_module_backward(roi_feat, rois, params, d_out, nongt_dim=None, ind
         a3_2d = a3.view(B * N, 3 * d)
         d_f = ops.gemm_nt(a3_2d, sink.wcat_t, resid=None if sink.resid is None else sink.resid.reshape(B * N, Fd)).reshape(B, N, Fd)
         sink.wgrad(a3_2d, f.reshape(B * N, Fd))
-        from . import train_ops as _T
         _T.colsum_add(a3_2d[:, :2 * d], *sink.b_qk)
         if sink.b_out is not None:
             _T.colsum_add(dY.reshape(B * N, d), *sink.b_out)
@@ -286,10 +309,7 @@ def attention_module_backward(roi_feat, rois, params, d_out, nongt_dim=None, ind
     dqk[:, :, :d] = dq
     dqk[:, :M, d:] = dk
     dvw_t = dvw.to(dtype)
-    wqk_t = getattr(mod, 'wqk_t', None)                                  # [Fd, 2d]: the trainer's per-step copies when present
-    wout_t = getattr(mod, 'wout_t', None)                                # [Fd, d]
-    wqk_t = ops.transpose_2d(mod.wqk) if wqk_t is None else wqk_t
-    wout_t = ops.transpose_2d(mod.wout) if wout_t is None else wout_t
+    wqk_t, wout_t = ops.transpose_2d(mod.wqk), ops.transpose_2d(mod.wout)       # [Fd, 2d], [Fd, d]
     d_f = ops.gemm_nt(dqk.reshape(B * N, 2 * d), wqk_t, out_dtype=torch.float32).reshape(B, N, Fd)
     d_fk = ops.gemm_nt(dvw_t.reshape(B * M, d), wout_t, out_dtype=torch.float32).reshape(B, M, Fd)
     d_f[:, :M] += d_fk
@@ -315,3 +335,70 @@ def attention_module_backward(roi_feat, rois, params, d_out, nongt_dim=None, ind
         'pair_pos_fc1_%d_weight' % i: dwp, 'pair_pos_fc1_%d_bias' % i: dbp,
     }
     return grads
+
+
+class BoxHeadTrain(object):
+    """Train branch of the box head and its adjoint, on a Trainer's parameters (as learn_nms.LearnNMSTrain is for the learn-NMS head).
+    The trainer owns the parameters, their relayout entries and the gradient buffers; this class reaches them through w / b / wt,
+    _wg / _bg, _add_bgrad, _scratch, _relayout.get, the W / Bv gradient views and deterministic.  The head holds VIEWS of the flat
+    buffers: the optimizer updates them in place, nothing is rebuilt or repacked per step but the [64, 32] pair_pos matrix."""
+
+    def __init__(self, trainer):
+        t = self.t = trainer
+        mods = [SimpleNamespace(wqk=t.w('qk_%d' % i), bqk=t.b('qk_%d' % i), wout=t.w('linear_out_%d' % i), bout=t.b('linear_out_%d' % i),
+                                wp=t.W.view(t.W.master, 'pair_pos_fc1_%d' % i), bp=t.b('pair_pos_fc1_%d' % i)) for i in (1, 2)] if t.relation else None
+        self.head = BoxHead(t.w('fc_new_1'), t.b('fc_new_1'), t.w('fc_new_2'), t.b('fc_new_2'), t.w('cls_bbox'), t.b('cls_bbox'), t.num_classes, mods)
+
+    def forward(self, pooled2, rois_t, N, key_count=None):
+        """pooled2 [B*R, 12544] bf16, rois_t [B,R,5] with the N non-gt rows (the keys of both modules) first -> the context of
+        `backward`: BoxHead.run's namespace (cls_score / bbox_pred contiguous) + pooled2, rois, N, key_count, mods, caches."""
+        h, bias, caches = self.head, (None, None), [{}, {}]         # caches: Q|K and VW^T projections of the forward, reused by the backward
+        if h.mods is not None:
+            # float32 ln G for the training forward (not the fp16 matrix-core bias of inference): the backward needs exactly this G
+            # and the outputs computed from it (attention_module_backward), so they are produced once, here
+            bias = ops.geometry_bias(rois_t, *pack_pair_pos(h.mods, rois_t.device), N, fast32=True)
+        s = h.run(pooled2, rois_t.shape[0], N, bias, rois_t, key_count, want_y=True, caches=caches)
+        s.cls_score, s.bbox_pred = s.cls_score.contiguous(), s.bbox_pred.contiguous()
+        s.pooled2, s.rois, s.N, s.key_count, s.mods, s.caches, s.bias = pooled2, rois_t, N, key_count, h.mods, caches, bias
+        return s
+
+    def sink(self, i, resid):
+        """GradSink of relation module i from the flat-buffer names: d[Wq; Wk; Wout] is ONE [3 d, Fd] view over the adjacent qk_i and
+        linear_out_i slices (queued for the bucket's grouped weight-gradient launch), the rel_cat_i relayout group is its transposed operand."""
+        t = self.t
+        (oq, sq), (oo, so) = t.W.slices['qk_%d' % i], t.W.slices['linear_out_%d' % i]
+        wcat_t = t._relayout.get('rel_cat_%d' % i)
+        assert wcat_t is not None and oo == oq + sq[0] * sq[1]          # (linear_out_i is registered right after qk_i)
+        g3 = t.W.grad[oq:oq + (sq[0] + so[0]) * sq[1]].view(sq[0] + so[0], sq[1])
+        queue = t._wg('qk_%d' % i)[2]
+        return GradSink(wcat_t, resid, lambda dy2d, x2d: _T._wg_call((g3, None, queue), dy2d, x2d), t._bg('qk_%d' % i), t._bg('linear_out_%d' % i),
+                        t.W.view(t.W.grad, 'pair_pos_fc1_%d' % i), t.Bv.view(t.Bv.grad, 'pair_pos_fc1_%d' % i), t._scratch,
+                        deterministic=t.deterministic)
+
+    def _act_bwd(self, s, i, d_x):
+        """x_i = relu(f_i + relation_i(f_i)) (plain head: relu(f_i)): d x_i [B,R,1024] -> d f_i (bf16, residual path + module path); the
+        module's parameter gradients go straight into the flat buffers (GradSink)."""
+        g = _T.relu_bwd(d_x.contiguous(), (s.x1, s.x2)[i - 1])
+        if s.mods is None:
+            return g
+        return attention_module_backward((s.f1, s.f2)[i - 1], s.rois, None, g, nongt_dim=s.N, index=i, dtype=torch.bfloat16, packed=s.mods[i - 1],
+                                         key_count=s.key_count, cache=s.caches[i - 1], sink=self.sink(i, g))['d_roi_feat']
+
+    def _fc_bwd(self, name, x2d, d_y2d):
+        t = self.t
+        d_x, dw, db = _T.linear_bwd(x2d, t.w(name), d_y2d, w_t=t.wt(name), keep_splits=True, wgrad_to=t._wg(name), bgrad_to=t._bg(name))
+        t._add_bgrad(name, db)
+        return d_x
+
+    def backward(self, s, d_cls, d_bbox, d_x2_extra=None):
+        """d cls_score [B,R,C] / d bbox_pred fp32 (+ d_x2_extra [B,N,1024]: a second consumer's gradient of fc_all_2_relu's first N rows,
+        the learn-NMS head's) -> d_pool [B*R, 12544] bf16; every parameter gradient of the head is accumulated or queued."""
+        B, R = s.x2.shape[0], s.x2.shape[1]
+        d_cb = torch.cat([d_cls, d_bbox], 2).reshape(B * R, -1).to(torch.bfloat16)
+        d_x2 = self._fc_bwd('cls_bbox', s.x2.reshape(B * R, -1), d_cb).reshape(B, R, -1)
+        if d_x2_extra is not None:
+            d_x2[:, :s.N] += d_x2_extra.to(d_x2.dtype)
+        d_f2 = self._act_bwd(s, 2, d_x2)
+        d_x1 = self._fc_bwd('fc_new_2', s.x1.reshape(B * R, -1), d_f2.reshape(B * R, -1)).reshape(B, R, -1)
+        d_f1 = self._act_bwd(s, 1, d_x1)
+        return self._fc_bwd('fc_new_1', s.pooled2, d_f1.reshape(B * R, -1))

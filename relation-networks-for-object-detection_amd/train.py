@@ -21,15 +21,13 @@ MI355X-first choices:
     recomputed from their inputs instead of storing [16, N, M] maps.
 """
 
-from types import SimpleNamespace
-
 import numpy as np
 import torch
 
 from . import ops, losses, train_ops as T
 from . import dist as D
 from .backbone import unit_names, conv_bn_names, fold_bn, EPS
-from .relation import attention_module_backward, _module_forward, pack_pair_pos, GradSink
+from .relation import BoxHeadTrain
 from .detector import Config, fc1_channels_last_perm
 from .learn_nms import LearnNMSTrain, rank_embedding
 from .pooling import RoiPooling
@@ -400,6 +398,7 @@ class Trainer(object):
         # separate relnet_relu_bwd pass over three [pixels, 4 mid] maps per unit (off for the float32 trunk)
         self.mask_epilogue = not self.trunk_fp32
         self._scratch_bufs = {}
+        self._box_head = BoxHeadTrain(self)
 
     # ---- accessors ----------------------------------------------------------------------------------------
     def _trunk32(self, name):
@@ -788,28 +787,8 @@ class Trainer(object):
         Returns (d_pool [B*R,12544] bf16, (x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem))."""
         c = self.cfg
         B, R = rois_t.shape[0], rois_t.shape[1]
-        # keys of both relation modules = the first N rows of each image
-        bt = torch.bfloat16
-        if self.relation:
-            mods = [self._rel_params(i) for i in (1, 2)]
-            wp_t, bp = pack_pair_pos(mods, self.device)
-            # float32 ln G for the training forward (not the fp16 matrix-core bias of inference): the backward needs exactly this G
-            # and the outputs computed from it (relation.attention_module_backward), so they are produced once, here
-            bias = ops.geometry_bias(rois_t, wp_t, bp, N, fast32=True)
-            f1 = ops.gemm_nt(pooled2, self.w('fc_new_1'), self.b('fc_new_1')).reshape(B, R, -1)
-            caches = [{}, {}]           # Q|K and VW^T projections of the forward, reused by the backward
-            # (VW^T buffers: persistent -- only columns [:N] are written, the pad columns stay zero from step to step: no per-step fill)
-            vw_ = lambda i: self._scratch('vwt_%d_%d' % (i, N), (B, mods[0].wout.shape[0], bias.shape[-1]), bt)     # keyed on N: a smaller N in the same padded width would inherit stale columns
-            _, x1, _ = _module_forward(f1, mods[0], bias[0], N, True, True, False, vwt_buf=vw_(1), key_count=key_count, cache=caches[0])
-            f2 = ops.gemm_nt(x1.reshape(B * R, -1), self.w('fc_new_2'), self.b('fc_new_2')).reshape(B, R, -1)
-            _, x2, _ = _module_forward(f2, mods[1], bias[1], N, True, True, False, vwt_buf=vw_(2), key_count=key_count, cache=caches[1])
-        else:       # plain 2FC head (resnet_v1_101_rcnn.py:96-174 / ..._learn_nms_1024_...:176-216): fc_new_i + ReLU in the GEMM epilogue
-            x1 = ops.gemm_nt(pooled2, self.w('fc_new_1'), self.b('fc_new_1'), relu=True).reshape(B, R, -1)
-            x2 = ops.gemm_nt(x1.reshape(B * R, -1), self.w('fc_new_2'), self.b('fc_new_2'), relu=True).reshape(B, R, -1)
-            f1 = x1
-        cb = ops.gemm_nt(x2.reshape(B * R, -1), self.w('cls_bbox'), self.b('cls_bbox'), out_dtype=torch.float32).reshape(B, R, -1)
-        nc = self.num_classes
-        cls_score, bbox_pred = cb[:, :, :nc].contiguous(), cb[:, :, nc:].contiguous()
+        h = self._box_head.forward(pooled2, rois_t, N, key_count)
+        x2, f1, cls_score, bbox_pred = h.x2, h.f1, h.cls_score, h.bbox_pred
         if getattr(c, 'enable_ohem', True):
             labels_ohem, weights_ohem = ops.box_annotator_ohem(cls_score, bbox_pred, label, bbox_target, bbox_weight, c.batch_rois_ohem)
             box_norm = c.batch_rois_ohem
@@ -835,26 +814,7 @@ class Trainer(object):
             out.update(lo)
         if self.lnms_only:          # every parameter in front of the learn-NMS head is fixed: nothing is differentiated past this point
             return None, (x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem)
-        # ================= backward =================
-        d_cb = torch.cat([d_cls, d_bbox], 2).reshape(B * R, -1).to(bt)
-        d_x2, dw, db = T.linear_bwd(x2.reshape(B * R, -1), self.w('cls_bbox'), d_cb, w_t=self.wt('cls_bbox'), keep_splits=True, wgrad_to=self._wg('cls_bbox'), bgrad_to=self._bg('cls_bbox'))
-        self._add_bgrad('cls_bbox', db)
-        if d_x2_lnms is not None:
-            d_x2 = d_x2.reshape(B, R, -1)
-            d_x2[:, :N] += d_x2_lnms.to(d_x2.dtype)
-        if self.relation:
-            d_f2 = self._relation_bwd(2, mods[1], f2, x2, rois_t, d_x2.reshape(B, R, -1), N, key_count, caches[1])
-        else:
-            d_f2 = T.relu_bwd(d_x2.reshape(B, R, -1).contiguous(), x2)
-        d_x1, dw, db = T.linear_bwd(x1.reshape(B * R, -1), self.w('fc_new_2'), d_f2.reshape(B * R, -1), w_t=self.wt('fc_new_2'), keep_splits=True, wgrad_to=self._wg('fc_new_2'), bgrad_to=self._bg('fc_new_2'))
-        self._add_bgrad('fc_new_2', db)
-        if self.relation:
-            d_f1 = self._relation_bwd(1, mods[0], f1, x1, rois_t, d_x1.reshape(B, R, -1), N, key_count, caches[0])
-        else:
-            d_f1 = T.relu_bwd(d_x1.reshape(B, R, -1).contiguous(), x1)
-        d_pool, dw, db = T.linear_bwd(pooled2, self.w('fc_new_1'), d_f1.reshape(B * R, -1), w_t=self.wt('fc_new_1'), keep_splits=True, wgrad_to=self._wg('fc_new_1'), bgrad_to=self._bg('fc_new_1'))
-        self._add_bgrad('fc_new_1', db)
-        return d_pool, (x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem)
+        return self._box_head.backward(h, d_cls, d_bbox, d_x2_lnms), (x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem)
 
     def _lnms_forward_backward(self, cls_score, bbox_pred, rois, im_info, feat, gt_boxes, num_gt, n_valid=None, d_cls_out=None):
         """Train branch of the learn-NMS head and its adjoint: learn_nms.LearnNMSTrain.__call__ (arguments and return values there)."""
@@ -868,29 +828,6 @@ class Trainer(object):
         w = self.w(name)
         cin = w.shape[1] // 9
         return w.view(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).reshape(cin, 9 * cout).contiguous()
-
-    def _rel_params(self, i):
-        return SimpleNamespace(wqk=self.w('qk_%d' % i), bqk=self.b('qk_%d' % i), wout=self.w('linear_out_%d' % i), bout=self.b('linear_out_%d' % i),
-                               wqk_t=self.wt('qk_%d' % i), wout_t=self.wt('linear_out_%d' % i),
-                               wp=self.W.view(self.W.master, 'pair_pos_fc1_%d' % i), bp=self.b('pair_pos_fc1_%d' % i))
-
-    def _relation_bwd(self, i, mod, f, x_act, rois, d_x, N, key_count=None, cache=None):
-        """x_act = relu(f + relation_i(f)); returns d f (bf16, residual path + module path) and accumulates the module's parameter
-        gradients straight into the flat buffers (relation.GradSink: one pack kernel, one projection-backward GEMM with the residual
-        gradient in its epilogue, one queued weight-gradient product for [Wq; Wk; Wout], column-sum kernels for the biases)."""
-        g = T.relu_bwd(d_x.contiguous(), x_act)
-        oq, sq = self.W.slices['qk_%d' % i]
-        oo, so = self.W.slices['linear_out_%d' % i]
-        wcat_t = self._relayout.get('rel_cat_%d' % i)
-        assert wcat_t is not None and oo == oq + sq[0] * sq[1]          # (linear_out_i is registered right after qk_i)
-        g3 = self.W.grad[oq:oq + (sq[0] + so[0]) * sq[1]].view(sq[0] + so[0], sq[1])      # d[Wq; Wk; Wout], adjacent slices of the flat buffer
-        sink = GradSink(wcat_t, g, lambda dy2d, x2d: T._wg_call((g3, None, self._wq), dy2d, x2d),
-                        self._bg('qk_%d' % i), self._bg('linear_out_%d' % i),
-                        self.W.view(self.W.grad, 'pair_pos_fc1_%d' % i), self.Bv.view(self.Bv.grad, 'pair_pos_fc1_%d' % i), self._scratch,
-                        deterministic=self.deterministic)
-        r = attention_module_backward(f, rois, None, g, nongt_dim=N, index=i, dtype=torch.bfloat16, packed=mod, key_count=key_count,
-                                      cache=cache, sink=sink)
-        return r['d_roi_feat']
 
     # ---- checkpoint view -----------------------------------------------------------------------------------
     def export_params(self):

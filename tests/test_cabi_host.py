@@ -76,6 +76,18 @@ def test_model_code_reaches_the_kernels_through_front_ends_only():
         assert not bad, bad
 
 
+def test_trainer_holds_no_box_head_code():
+    """The box head's forward and adjoint live in relation.py (BoxHead, BoxHeadTrain): train.py imports none of their building blocks and
+    defines neither of the two methods that used to hold the adjoint."""
+    import ast
+    tree = ast.parse(open(os.path.join(ROOT, 'relation-networks-for-object-detection_amd', 'train.py')).read(), 'train.py')
+    imported = {a.name for n in ast.walk(tree) if isinstance(n, (ast.Import, ast.ImportFrom)) for a in n.names}
+    assert not imported & {'_module_forward', 'GradSink', 'attention_module_backward', 'pack_pair_pos'}, imported
+    defined = {n.name for n in ast.walk(tree) if isinstance(n, (ast.FunctionDef, ast.ClassDef))}
+    assert not defined & {'_relation_bwd', '_rel_params'}, defined
+    assert 'BoxHeadTrain' in imported and '_head_forward_backward' in defined
+
+
 def test_proposal_prop_protocol():
     import relnet_amd  # noqa: F401
     from relnet_amd import operator_py
