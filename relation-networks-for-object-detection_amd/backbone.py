@@ -11,14 +11,19 @@ graph itself: the Caffe-style ResNet (stride on the FIRST 1x1 of a stage, :99,10
 (:632-633), ceil-mode pool1 (pooling_convention='full', :35-36) and the frozen BatchNorm (use_global_stats=True, eps=1e-5,
 :32) folded into the preceding convolution at load time.
 Parameter names are the reference's (`res4b7_branch2a_weight`, `bn4b7_branch2a_gamma`, ...).
+
+The wiring is written once, as functions over a path's conv callable: `walk_units` (where conv4 and the stage ends are taken),
+`bottleneck_unit`, `fpn_neck`, `rpn_head`.  `Backbone` runs them for inference; `TrunkTrain` runs them on a Trainer's weights, keeps the
+activations, and holds the adjoint of each beside it.
 """
 import math
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, train_ops as T
 
 UNITS = (3, 4, 23, 3)
 FILTERS = (256, 512, 1024, 2048)
@@ -116,6 +121,69 @@ def fold_bn(w, gamma, beta, mean, var, eps=EPS):
     """BatchNorm(use_global_stats=True, fix_gamma=False): y = (x-mean)/sqrt(var+eps)*gamma+beta."""
     s = gamma.double() / torch.sqrt(var.double() + eps)
     return (w.double() * s.view(-1, 1, 1, 1)).float(), (beta.double() - mean.double() * s).float()
+
+
+# ---- the graph, written once.  Every path (bf16 HIP kernels, exact-fp32 kernels, library convolutions, the training step) hands in its own
+# conv(x, name, stride=1, pad=0, dil=1, relu=False, resid=None, out_dtype=None): layer `name` on x with bias (+ shortcut) (+ ReLU) in that
+# path's layout and kernels.  What the functions below own is the wiring.
+
+def walk_units(units, x, unit_fn, at_conv4=None):
+    """x through `units` (rows of unit_names) by x = unit_fn(x, unit).  conv4 is the input of the first res5 unit -- at_conv4(conv4) is called
+    there, before res5 is queued (the RPN branch forks at that point) -- and ends[s] the output of stage s, taken in front of the
+    projection unit of stage s + 1 (the FPN laterals).  -> (output of the last unit, conv4, ends)"""
+    conv4, ends = None, {}
+    for unit in units:
+        stage, proj = unit[0], unit[7]
+        if stage == 5 and conv4 is None:
+            conv4 = x
+            if at_conv4 is not None:
+                at_conv4(conv4)
+        if proj and stage > 2:
+            ends[stage - 1] = x
+        x = unit_fn(x, unit)
+    return x, conv4, ends
+
+
+def bottleneck_unit(conv, x, unit, y_pre=None, sc=None, deform=None, expand=None, kept=None):
+    """One bottleneck unit (resnet_v1_101_rcnn_base.py: branch1 | branch2a -> 2b -> 2c, + shortcut, ReLU).
+    y_pre: the reduce output, when the previous unit's chain kernel already produced it.  sc: the shortcut operand, when the caller made it.
+    deform(y1, name) -> (y2, off): the deformable 3x3 of a res5 unit with its offset convolution, in the caller's layout.
+    expand(y2, sc) -> (x_next, reduce output of the NEXT unit | None), or None: a chain kernel in place of expand + shortcut + ReLU.
+    kept: a list that receives y1, y2, off (what a training step keeps for the adjoint).  Without it each inner activation is released
+    as soon as the next layer has read it, so the allocator hands its block to the layer after that.
+    -> (x_next, next unit's reduce output | None)"""
+    stage, nm, ic, mc, oc, stride, dil, proj = unit
+    if sc is None:
+        sc = conv(x, 'res%s_branch1' % nm, stride=stride) if proj else x
+    y = y_pre if y_pre is not None else conv(x, 'res%s_branch2a' % nm, stride=stride, relu=True)
+    if kept is not None:
+        kept.append(y)
+    if deform is not None and stage == 5:
+        y, off = deform(y, 'res%s_branch2b' % nm)
+    else:
+        y, off = conv(y, 'res%s_branch2b' % nm, pad=dil, dil=dil, relu=True), None
+    if kept is not None:
+        kept.extend((y, off))
+    del off
+    out = expand(y, sc) if expand is not None else None
+    if out is None:
+        out = conv(y, 'res%s_branch2c' % nm, relu=True, resid=sc), None      # relu(bn(conv) + shortcut)
+    return out
+
+
+def fpn_neck(conv, upsample_add, conv5, ends):
+    """Top-down pathway (symbols/..._fpn_...:804-840): 1x1 laterals, upsample_add(lateral, coarser top) = nearest 2x upsampling + sum,
+    3x3 output convolutions.  -> (tops, feats), both {4, 8, 16, 32: map}."""
+    tops = {32: conv(conv5, 'fpn_ft32_1x1')}
+    for lvl, src in ((16, ends[4]), (8, ends[3]), (4, ends[2])):
+        tops[lvl] = upsample_add(conv(src, 'fpn_ft%d_1x1' % lvl), tops[lvl * 2])
+    return tops, {lvl: conv(tops[lvl], 'fpn_ft%d_3x3' % lvl, pad=1) for lvl in (4, 8, 16, 32)}
+
+
+def rpn_head(conv, conv4):
+    """-> (r = relu(rpn_conv_3x3(conv4)), the fused [.., 2A | 4A] score | delta map of the two 1x1 outputs, float32 on the HIP kernels)."""
+    r = conv(conv4, 'rpn_conv_3x3', pad=1, relu=True)
+    return r, conv(r, 'rpn_out', out_dtype=torch.float32)
 
 
 class Backbone(object):
@@ -235,6 +303,8 @@ class Backbone(object):
                 self.wf[name] = ops.pack_w_frag(self.wp[name][0])
 
     def _hconv(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None, out_dtype=None):
+        if name in self.halo3 and stride == 1:      # 64-channel 3x3 (res2 branch2b): the halo-resident kernel
+            return ops.conv3x3_halo(x.contiguous(), *self.halo3[name], relu=relu)
         w, b, k = self.wp[name]
         return ops.conv2d_nhwc(x, w, b, ksize=k, stride=stride, pad=pad, dil=dil, relu=relu, resid=resid,
                                out_dtype=out_dtype, w_frag=self.wf.get(name))
@@ -275,57 +345,59 @@ class Backbone(object):
             x = self._float_image(data, im_info, torch.float32).to(self.dtype).contiguous(memory_format=self.mf)
             x = F.conv2d(x, self.w['conv1'][0], None, stride=2, padding=3)
             x = ops.stem_bias_relu_pool(x.permute(0, 2, 3, 1), self.b32['conv1'])
-        conv4 = None
-        ends = {}
-        y_next = None
         side, hooked = None, None
         self.last_chain_units, self.last_side_stream, self.last_stage_split = [], False, {}      # what actually ran (reported by oracle/parity.py)
         self.last_quarter_units = []
+        after = dict(zip(self.units, self.units[1:]))
+        y_next = None
         compact = False                   # x is the even-pixel quarter of the previous stage's output (its last unit ran in the quarter form)
-        ui = 0
-        while ui < len(self.units):
-            unit = self.units[ui]
+        split = None                      # the stage that ran whole, in sub-batches, at its first unit
+
+        def fork(conv4):                  # RPN head + hook next to res5
+            nonlocal side, hooked
+            if rpn_hook is None or self.fpn:
+                return
+            main = torch.cuda.current_stream()
+            side = self._side_stream()
+            self.last_side_stream = True
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                hooked = self._rpn_head(conv4)
+                hooked = hooked + (rpn_hook(hooked[0], hooked[1]),)
+
+        def unit_fn(x, unit):             # which kernels run a unit: stage split, quarter form, in-place expand
+            nonlocal y_next, compact, split
             stage, proj = unit[0], unit[7]
-            if stage == 5 and conv4 is None:
-                conv4 = x
-                if rpn_hook is not None and not self.fpn:      # fork: RPN head + hook next to res5
-                    main = torch.cuda.current_stream()
-                    side = self._side_stream()
-                    self.last_side_stream = True
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        hooked = self._rpn_head(conv4)
-                        hooked = hooked + (rpn_hook(hooked[0], hooked[1]),)
-            if proj and stage > 2:
-                ends[stage - 1] = x
+            if stage == split:
+                return x
             nsplit = self._stage_split(stage, x, unit) if proj else 1
             if nsplit > 1:
                 # Infinity-Cache-sized sub-batches (see _stage_split): all units of the stage on images [lo, hi), then the next range
-                stage_units = [u for u in self.units if u[0] == stage]
-                x = self._run_stage_split(x, stage_units, nsplit)
-                ui += len(stage_units)
-                continue
-            quarter = self._quarter_ok(x, unit, self.units[ui + 1] if ui + 1 < len(self.units) else None)
+                split = stage
+                return self._run_stage_split(x, [u for u in self.units if u[0] == stage], nsplit)
+            quarter = self._quarter_ok(x, unit, after.get(unit))
             x, y_next = self._unit_hip(x, unit, y_next, inplace=self.inplace_expand, quarter=quarter, subsampled=compact)
             compact = quarter
-            ui += 1
-        conv5 = x
-        nchw = lambda t: t.permute(0, 3, 1, 2)
+            return x
+
+        conv5, conv4, ends = walk_units(self.units, x, unit_fn, fork)
+        return self._outputs(self._hconv, conv5, conv4, ends, lambda t: t.permute(0, 3, 1, 2), ops.upsample2x_add_, hooked, side)
+
+    def _outputs(self, conv, conv5, conv4, ends, nchw, upsample_add, hooked=None, side=None):
+        """What hangs off the trunk, as `forward`'s dictionary: the FPN neck, or conv_new_1 + the RPN head (`hooked`: the head ran on the
+        side stream with the caller's hook behind it).  nchw: this path's activation layout -> logical NCHW."""
         if self.fpn:
-            # top-down pathway: 1x1 laterals, nearest 2x upsampling + sum (one in-place kernel), 3x3 output convs
-            tops = {32: self._hconv(conv5, 'fpn_ft32_1x1')}
-            for lvl, src in ((16, ends[4]), (8, ends[3]), (4, ends[2])):
-                tops[lvl] = ops.upsample2x_add_(self._hconv(src, 'fpn_ft%d_1x1' % lvl), tops[lvl * 2])
-            out = {'fpn_ft%d' % lvl: nchw(self._hconv(tops[lvl], 'fpn_ft%d_3x3' % lvl, pad=1)) for lvl in (4, 8, 16, 32)}
+            _, feats = fpn_neck(conv, upsample_add, conv5, ends)
+            out = {'fpn_ft%d' % lvl: nchw(feats[lvl]) for lvl in (4, 8, 16, 32)}
             out.update(conv4=nchw(conv4), conv5=nchw(conv5))
             return out
-        feat = self._hconv(conv5, 'conv_new_1', relu=True)
+        feat = conv(conv5, 'conv_new_1', relu=True)
         out = dict(conv4=nchw(conv4), conv5=nchw(conv5), conv_new_1_relu=nchw(feat))
         if hooked is not None:
             torch.cuda.current_stream().wait_stream(side)      # join
             out.update(rpn_cls_score=hooked[0], rpn_bbox_pred=hooked[1], rpn_hook=hooked[2])
         else:
-            out['rpn_cls_score'], out['rpn_bbox_pred'] = self._rpn_head(conv4)
+            out['rpn_cls_score'], out['rpn_bbox_pred'] = self._rpn_head(conv4, conv, nchw)
         return out
 
     #: stage -> sub-batches (default: none).  Measured in round 4 and NOT adopted: running the 23 res4 units on two 27-image halves so
@@ -405,40 +477,28 @@ class Backbone(object):
             return ops.bottleneck_chain_s2(y, x.contiguous(), w3f, b3), None
         fuse_proj = (nm in self.chain_proj and sc_out is None and x.is_contiguous()
                      and (force_chain or ops.chain_worthwhile(x.numel() // x.shape[-1], mc)))
+        sc = None
         if fuse_proj:
-            sc = None                # res2a: the projection is computed inside the expand kernel
-        elif proj:
+            sc = x                   # res2a: the expand kernel projects its shortcut operand itself
+        elif proj and sc_out is not None:
             w, b, k = self.wp['res%s_branch1' % nm]
             sc = ops.conv2d_nhwc(x, w, b, ksize=k, stride=stride, out=sc_out)
-        else:
-            sc = x
-        y = y_pre if y_pre is not None else self._hconv(x, 'res%s_branch2a' % nm, stride=stride, relu=True)
-        if self.dcn and stage == 5:
-            y = self._deform_2b(y.permute(0, 3, 1, 2), 'res%s_branch2b' % nm,
-                                self._hconv(y, 'res%s_branch2b_offset' % nm, pad=2, dil=2, out_dtype=torch.float32).permute(0, 3, 1, 2))
-            y = y.permute(0, 2, 3, 1)
-        elif ('res%s_branch2b' % nm) in self.halo3:
-            y = ops.conv3x3_halo(y.contiguous(), *self.halo3['res%s_branch2b' % nm], relu=True)
-        else:
-            y = self._hconv(y, 'res%s_branch2b' % nm, pad=dil, dil=dil, relu=True)
-        if fuse_proj:
-            if nm not in self.last_chain_units:
-                self.last_chain_units.append(nm)
-            return ops.bottleneck_chain_proj(y, x, *self.chain_proj[nm])
-        ch = self.chain.get(nm)
-        if ch is not None and not force_chain and not ops.chain_worthwhile(y.numel() // y.shape[-1], y.shape[-1]):
-            ch = None            # small maps (B = 1, late stages at small B): the tiled convolution kernels fill the GPU better
-        if ch is not None:       # expand + shortcut + ReLU and the next unit's reduce + ReLU in one pixel-wise kernel
+
+        def chain(y, sc):            # expand + shortcut + ReLU and the next unit's reduce + ReLU in one pixel-wise kernel
+            ch = self.chain.get(nm)
+            if not fuse_proj and (ch is None or not (force_chain or ops.chain_worthwhile(y.numel() // y.shape[-1], y.shape[-1]))):
+                return None          # small maps (B = 1, late stages at small B): the tiled convolution kernels fill the GPU better
             if nm not in self.last_chain_units:
                 self.last_chain_units.append(nm)  # (a split stage, `inplace`, is only entered when every CU gets a 256-pixel set)
+            if fuse_proj:
+                return ops.bottleneck_chain_proj(y, x, *self.chain_proj[nm])
             return ops.bottleneck_chain(y, sc.contiguous(), *ch, inplace=inplace and sc.is_contiguous())
-        return self._hconv(y, 'res%s_branch2c' % nm, relu=True, resid=sc), None     # relu(bn(conv) + shortcut)
+        return bottleneck_unit(self._hconv, x, unit[:5] + (stride,) + unit[6:], y_pre, sc, self._deform_nhwc(self._hconv), chain)
 
-    def _rpn_head(self, conv4):
-        r = self._hconv(conv4, 'rpn_conv_3x3', pad=1, relu=True)
-        rpn = self._hconv(r, 'rpn_out', out_dtype=torch.float32)
+    def _rpn_head(self, conv4, conv=None, nchw=lambda t: t.permute(0, 3, 1, 2)):
+        rpn = nchw(rpn_head(conv or self._hconv, conv4)[1])
         na2 = self.w['rpn_cls_score'][0].shape[0]
-        return rpn[..., :na2].permute(0, 3, 1, 2), rpn[..., na2:].permute(0, 3, 1, 2)
+        return rpn[:, :na2], rpn[:, na2:]
 
     def _side_stream(self):
         if getattr(self, '_side', None) is None:
@@ -451,12 +511,25 @@ class Backbone(object):
         w, b = self.wp_dcn[name]
         return ops.deformable_conv(y, offset, w, b, 3, 1, 2, 2, 4, relu=True)
 
-    def _conv(self, x, name, stride=1, pad=0, dil=1, relu=False):
+    def _deform_nhwc(self, conv):
+        """bottleneck_unit's `deform` for the NHWC paths (None without dcn): offset convolution on `conv`, then `_deform_2b`."""
+        if not self.dcn:
+            return None
+
+        def deform(y, name):
+            off = conv(y, name + '_offset', pad=2, dil=2, out_dtype=torch.float32)
+            return self._deform_2b(y.permute(0, 3, 1, 2), name, off.permute(0, 3, 1, 2)).permute(0, 2, 3, 1), off
+        return deform
+
+    def _conv(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None, out_dtype=None):
+        """(out_dtype is the HIP kernels' argument: the library path and the float32 path keep their own type)"""
         w, b = self.w[name]
         y = F.conv2d(x, w, b, stride=stride, padding=pad, dilation=dil)
+        if resid is not None:
+            y.add_(resid)
         return F.relu_(y) if relu else y
 
-    def _c32(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None):
+    def _c32(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None, out_dtype=None):
         w, b, k = self.wp32[name]
         return ops.conv2d_nhwc_f32(x, w, b, ksize=k, stride=stride, pad=pad, dil=dil, relu=relu, resid=resid)
 
@@ -468,37 +541,11 @@ class Backbone(object):
         x[..., :Cin] = data.permute(0, 2, 3, 1)
         x = self._c32(x, 'conv1', stride=2, pad=3, relu=True)
         x = ops.maxpool_nhwc_f32(x, 3, 2)
-        conv4, ends = None, {}
-        nchw = lambda t: t.permute(0, 3, 1, 2)
-        for stage, nm, ic, mc, oc, stride, dil, proj in self.units:
-            if stage == 5 and conv4 is None:
-                conv4 = x
-            if proj and stage > 2:
-                ends[stage - 1] = x
-            sc = self._c32(x, 'res%s_branch1' % nm, stride=stride) if proj else x
-            y = self._c32(x, 'res%s_branch2a' % nm, stride=stride, relu=True)
-            if self.dcn and stage == 5:
-                off = self._c32(y, 'res%s_branch2b_offset' % nm, pad=2, dil=2)
-                y = self._deform_2b(nchw(y), 'res%s_branch2b' % nm, nchw(off)).permute(0, 2, 3, 1)
-            else:
-                y = self._c32(y, 'res%s_branch2b' % nm, pad=dil, dil=dil, relu=True)
-            x = self._c32(y, 'res%s_branch2c' % nm, relu=True, resid=sc)
-        conv5 = x
+        deform = self._deform_nhwc(self._c32)
+        conv5, conv4, ends = walk_units(self.units, x, lambda x, unit: bottleneck_unit(self._c32, x, unit, deform=deform)[0])
         if self.frozen_only:
-            return x
-        if self.fpn:
-            tops = {32: self._c32(conv5, 'fpn_ft32_1x1')}
-            for lvl, src in ((16, ends[4]), (8, ends[3]), (4, ends[2])):
-                tops[lvl] = ops.upsample2x_add_(self._c32(src, 'fpn_ft%d_1x1' % lvl), tops[lvl * 2])
-            out = {'fpn_ft%d' % lvl: nchw(self._c32(tops[lvl], 'fpn_ft%d_3x3' % lvl, pad=1)) for lvl in (4, 8, 16, 32)}
-            out.update(conv4=nchw(conv4), conv5=nchw(conv5))
-            return out
-        feat = self._c32(conv5, 'conv_new_1', relu=True)
-        r = self._c32(conv4, 'rpn_conv_3x3', pad=1, relu=True)
-        rpn = self._c32(r, 'rpn_out')
-        na2 = self.w['rpn_cls_score'][0].shape[0]
-        return dict(conv4=nchw(conv4), conv5=nchw(conv5), conv_new_1_relu=nchw(feat),
-                    rpn_cls_score=nchw(rpn[..., :na2]), rpn_bbox_pred=nchw(rpn[..., na2:]))
+            return conv5
+        return self._outputs(self._c32, conv5, conv4, ends, lambda t: t.permute(0, 3, 1, 2), ops.upsample2x_add_)
 
     def forward(self, data, rpn_hook=None, im_info=None):
         """data [B,3,H,W] float NCHW (RGB, means subtracted: dataset/image.py:get_image), or [B,H,W,3] uint8 BGR HWC as decoded /
@@ -519,33 +566,233 @@ class Backbone(object):
         x = self._float_image(data, im_info, torch.float32).to(self.dtype).contiguous(memory_format=self.mf)
         x = self._conv(x, 'conv1', stride=2, pad=3, relu=True)
         x = F.max_pool2d(x, kernel_size=3, stride=2, padding=0, ceil_mode=True)
-        conv4 = None
-        ends = {}
-        for stage, nm, ic, mc, oc, stride, dil, proj in self.units:
-            if stage == 5 and conv4 is None:
-                conv4 = x
-            if proj and stage > 2:
-                ends[stage - 1] = x
-            sc = self._conv(x, 'res%s_branch1' % nm, stride=stride) if proj else x
-            y = self._conv(x, 'res%s_branch2a' % nm, stride=stride, relu=True)
-            if self.dcn and stage == 5:
-                off = self._conv(y, 'res%s_branch2b_offset' % nm, pad=2, dil=2).float()
-                y = self._deform_2b(y, 'res%s_branch2b' % nm, off).contiguous(memory_format=self.mf)
-            else:
-                y = self._conv(y, 'res%s_branch2b' % nm, pad=dil, dil=dil, relu=True)
-            y = self._conv(y, 'res%s_branch2c' % nm)
-            x = F.relu_(y.add_(sc))
-        conv5 = x
-        if self.fpn:
-            tops = {32: self._conv(conv5, 'fpn_ft32_1x1')}
-            for lvl, src in ((16, ends[4]), (8, ends[3]), (4, ends[2])):
-                tops[lvl] = F.interpolate(tops[lvl * 2], scale_factor=2, mode='nearest') + self._conv(src, 'fpn_ft%d_1x1' % lvl)
-            out = {'fpn_ft%d' % lvl: self._conv(tops[lvl], 'fpn_ft%d_3x3' % lvl, pad=1) for lvl in (4, 8, 16, 32)}
-            out.update(conv4=conv4, conv5=conv5)
+
+        def deform(y, name):
+            off = self._conv(y, name + '_offset', pad=2, dil=2).float()
+            return self._deform_2b(y, name, off).contiguous(memory_format=self.mf), off
+        conv5, conv4, ends = walk_units(self.units, x, lambda x, unit: bottleneck_unit(self._conv, x, unit, deform=deform if self.dcn else None)[0])
+        return self._outputs(self._conv, conv5, conv4, ends, lambda t: t, lambda lateral, top: F.interpolate(top, scale_factor=2, mode='nearest') + lateral)
+
+
+# workgroups of the RPN head's grouped weight-gradient launch on the side stream: a quarter of the chip, the head's kernels beside it keep
+# theirs (same box, 8 images: 16.99 ms per step with these products in the heads bucket's launch on the main stream, 16.92 on 32 workgroups,
+# 16.87 - 16.89 on 64, 16.99 on 128)
+RPN_WGRAD_WORKGROUPS = 64
+
+#: what the training forward keeps of one unit for its adjoint (off: (offset map, sampled column matrix) of a deformable unit | None)
+SavedUnit = namedtuple('SavedUnit', 'stage nm stride dil proj x y1 y2 out off')
+
+
+class TrunkTrain(object):
+    """res3 .. res5, the FPN neck and the RPN head convolutions of a training step, each with its adjoint beside it, on a Trainer's
+    parameters (as relation.BoxHeadTrain is for the box head).  The forwards are the functions above on the trainer's `_conv`; the trainer
+    owns the parameters, their relayout entries, the gradient buffers and the queues, reached through w / wt / b / conv_bias / bn_scale,
+    _wg / _bg / _add_wgrad / _add_bgrad and _bucket_ready, and it keeps chain_units, mask_epilogue, _fragpack and _relayout: all of them
+    are read when a method runs, so in-place optimizer updates and a flipped switch are seen without a rebuild."""
+
+    def __init__(self, trainer):
+        """Registers res3 .. res5's block boundaries for the inference chain kernels (csrc/bottleneck.hip): expand + shortcut + ReLU of unit u
+        and reduce + ReLU of unit u + 1 in one launch.  They read the weights in MFMA-fragment order; the trained weights change every
+        step, so ONE grouped launch per step (trainer._fragpack, an ops.FragRepack) rewrites those copies next to the data-gradient
+        layouts.  trainer.chain_units: unit -> (has_next_reduce, next unit).  (The float32 trunk keeps the per-layer convolution launches.)"""
+        t = self.t = trainer
+        t._fragpack, t.chain_units = ops.FragRepack(t.device), {}
+        if not t.trunk_fp32:
+            trainable = [u for u in t.units if u[0] >= 3]
+            for (st, nm, ic, mc, oc, stride, dil, proj), nxt in zip(trainable, trainable[1:] + [None]):
+                if t.cfg.dcn and st == 5:
+                    continue
+                with_reduce = nxt is not None and nxt[0] == st and not nxt[7] and mc in ops.CHAIN_MIDS
+                if not with_reduce and mc not in ops.CHAIN_EXPAND_MIDS:
+                    continue
+                t._fragpack.add('w3:' + nm, t.w('res%s_branch2c' % nm), 0)
+                if with_reduce:
+                    t._fragpack.add('w1:' + nxt[1], t.w('res%s_branch2a' % nxt[1]), 1)
+                t.chain_units[nm] = (with_reduce, nxt[1] if with_reduce else None)
+            t._fragpack.build()
+
+    def _dgrad_w(self, name, cout):
+        """[Cout, 9*Cin] packed forward weights -> [Cin, 9*Cout] tap-flipped data-gradient weights."""
+        wt = self.t.wt(name)
+        if wt is not None:
+            return wt
+        w = self.t.w(name)
+        cin = w.shape[1] // 9
+        return w.view(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).reshape(cin, 9 * cout).contiguous()
+
+    # ---- res3 .. res5 ----------------------------------------------------------------------------------------
+    def forward(self, data, at_conv4=None, im_info=None):
+        """Frozen stem + res2, then res3..res5 keeping every ReLU output.  Returns (conv5, conv4, saved units, stage ends).
+        at_conv4(conv4): called once conv4 exists, before res5 is queued (the RPN branch forks there).  data: float NCHW or uint8
+        [B,H,W,3] BGR HWC (Backbone.forward; im_info gives each image's extent)."""
+        t = self.t
+        x = t._frozen_backbone.forward_res2(data, im_info)      # (float32 NHWC for the float32 trunk: Backbone impl 'hip32')
+        saved = []
+        y_pre = None               # reduce output of the coming unit when the previous unit's chain kernel already produced it
+
+        def deform(y1, nb):        # 72-channel offset conv -> DeformableConvolution(num_deformable_group=4) + BN + ReLU
+            off = t._conv(y1, nb + '_offset', pad=2, dil=2, out_dtype=torch.float32)
+            y2, col = ops.deformable_conv(y1.permute(0, 3, 1, 2), off.permute(0, 3, 1, 2), t.w(nb), t.conv_bias[nb],
+                                          3, 1, 2, 2, 4, relu=True, want_col=True)
+            return y2.permute(0, 2, 3, 1), (off, col)      # (the sampled column matrix rides along to the backward: the weight gradient's X operand)
+
+        def unit_fn(x, unit):
+            nonlocal y_pre
+            nm, mc = unit[1], unit[3]
+
+            def chain(y2, sc):
+                ch = t.chain_units.get(nm)
+                if ch is None or not ops.chain_worthwhile(y2.numel() // y2.shape[-1], mc):
+                    return None
+                # expand + shortcut + ReLU and (inside a stage) the NEXT unit's reduce + ReLU in one pixel-wise kernel; every activation
+                # the backward needs (x_next, mid1_next) is still written, nothing is overwritten in place
+                w1f = t._fragpack.get('w1:' + ch[1]) if ch[0] else None
+                b1 = t.conv_bias['res%s_branch2a' % ch[1]] if ch[0] else None
+                return ops.bottleneck_chain(y2, sc.contiguous(), t._fragpack.get('w3:' + nm), w1f, t.conv_bias['res%s_branch2c' % nm], b1)
+            kept = []
+            out, y_pre = bottleneck_unit(t._conv, x, unit, y_pre, deform=deform if t.cfg.dcn else None, expand=chain, kept=kept)
+            y1, y2, off = kept
+            saved.append(SavedUnit(unit[0], nm, unit[5], unit[6], unit[7], x, y1, y2, out, off))
             return out
-        feat = self._conv(conv5, 'conv_new_1', relu=True)
-        r = self._conv(conv4, 'rpn_conv_3x3', pad=1, relu=True)
-        rpn = self._conv(r, 'rpn_out')
-        na2 = self.w['rpn_cls_score'][0].shape[0]
-        return dict(conv4=conv4, conv5=conv5, conv_new_1_relu=feat,
-                    rpn_cls_score=rpn[:, :na2], rpn_bbox_pred=rpn[:, na2:])
+        conv5, conv4, ends = walk_units([u for u in t.units if u[0] > 2], x, unit_fn, at_conv4)       # (res2 ran inside forward_res2)
+        ends[5] = conv5
+        return conv5, conv4, saved, ends
+
+    def backward(self, saved, d_x, inject):
+        """res5 -> res3 backward.  d_x = gradient of the last unit's output; inject[unit] = extra gradient of that unit's output."""
+        t = self.t
+        B = saved[0].x.shape[0]
+        bt = torch.bfloat16
+        # trunk: res5 -> res3.  Gradient buckets are announced as they complete (heads first; with DCN the res5 offset
+        # convolutions live in the heads bucket, which is then complete only after res5): dist.BucketedAllReduce overlaps
+        # each bucket's all-reduce with the rest of the backward pass
+        dcn = t.cfg.dcn
+        t._grad_buckets()
+        if not dcn:
+            t._bucket_ready('heads')
+        prev_bucket = None
+        masked = False            # d_x already carries the ReLU mask of the unit's output (relnet_gemm_nt_mask of the unit after it)
+        order = list(reversed(saved))
+        for pos, s in enumerate(order):
+            nm, x_in, y1, y2 = s.nm, s.x, s.y1, s.y2
+            bucket = t._unit_bucket[nm]
+            if prev_bucket is not None and bucket != prev_bucket:
+                if dcn and prev_bucket == 'res5':
+                    t._bucket_ready('res5', 'heads')        # both complete at this point: one cut, two collectives
+                else:
+                    t._bucket_ready(prev_bucket)
+            prev_bucket = bucket
+            n1, na, nb, nc_ = 'res%s_branch1' % nm, 'res%s_branch2a' % nm, 'res%s_branch2b' % nm, 'res%s_branch2c' % nm
+            if inject.get(nm) is not None:       # a second consumer of this unit's output (RPN head at conv4, FPN laterals)
+                assert not masked
+                d_x = inject[nm] if d_x is None else d_x + inject[nm]
+            g_out = d_x if masked else T.relu_bwd(d_x, s.out)
+            masked = False
+            # (ReLU masks of the two inner activations ride in the data-gradient kernels' epilogues)
+            g_y2, dw = T.conv1x1_bwd(y2, t.w(nc_), g_out, w_t=t.wt(nc_), keep_splits=True, wgrad_to=t._wg(nc_, t.bn_scale[nc_]), relu_mask=y2)
+            if s.off is not None:          # deformable branch2b: data + offset gradients, then the offset conv's own backward
+                off, col = s.off
+                gd, goff, dw = ops.deformable_conv_bwd(y1.permute(0, 3, 1, 2), off.permute(0, 3, 1, 2), t.w(nb),
+                                                       g_y2.permute(0, 3, 1, 2), 3, 1, 2, 2, 4, col=col)
+                t._add_wgrad(nb, dw, t.bn_scale[nb])
+                no = nb + '_offset'
+                goff_p = torch.zeros((B, off.shape[1], off.shape[2], 128), device=off.device, dtype=bt)   # 72 -> 128 channels
+                goff_p[..., :72] = goff
+                wd_ = t.w(no).view(72, 3, 3, -1).flip(1, 2).permute(3, 1, 2, 0)                     # [Cin,3,3,72]
+                wdp = torch.zeros((wd_.shape[0], 3, 3, 128), device=off.device, dtype=bt); wdp[..., :72] = wd_
+                d_off_in, dwo = T.conv3x3_bwd(y1, wdp.reshape(wd_.shape[0], -1).contiguous(), goff_p, dil=2, keep_splits=True)
+                t._add_wgrad(no, dwo.sum(0)[:72]); t._add_bgrad(no, goff.sum((0, 1, 2)))
+                d_y1 = (gd + d_off_in.float()).to(bt).contiguous()
+                g_y1 = T.relu_bwd(d_y1, y1)
+            else:
+                g_y1, dw = T.conv3x3_bwd(y1, self._dgrad_w(nb, y2.shape[3]), g_y2, dil=s.dil, keep_splits=True, wgrad_to=t._wg(nb, t.bn_scale[nb]),
+                                         relu_mask=y1)
+            prev_nm = order[pos + 1].nm if pos + 1 < len(order) else None
+            if s.proj:
+                first = s.stage == 3          # res3a: its input comes from the frozen res2 -> no data gradient
+                # both branches read the same (sampled) input: their data gradients are summed in the second GEMM's epilogue -- at the SAMPLED
+                # resolution for a stride-2 unit, then scattered to the input's resolution once, with the previous unit's ReLU mask in the same
+                # pass when that output has no other consumer (was: 2 zero fills + 2 strided copies + a full-resolution add + relu_bwd)
+                stride = s.stride
+                lr = stride != 1
+                # a second consumer's gradient of this unit's INPUT (the RPN head at conv4, in front of the stride-1 res5a) rides in the first
+                # GEMM's epilogue; the input's ReLU mask can then ride in the second one's
+                inj = inject.get(prev_nm) if (stride == 1 and not first and prev_nm is not None) else None
+                fold = inj is not None and inj.dtype == g_y1.dtype and tuple(inj.shape) == tuple(x_in.shape) and inj.is_contiguous()
+                d_a, dw = T.conv1x1_bwd(x_in, t.w(na), g_y1, stride=stride, need_dx=not first, w_t=t.wt(na), keep_splits=True, wgrad_to=t._wg(na, t.bn_scale[na]),
+                                        dx_add=inj if fold else None, low_res=lr)
+                if fold:
+                    inject = {k: v for k, v in inject.items() if k != prev_nm}
+                can_mask = t.mask_epilogue and not first and prev_nm is not None and inject.get(prev_nm) is None
+                d_s, dw = T.conv1x1_bwd(x_in, t.w(n1), g_out, stride=stride, need_dx=not first, w_t=t.wt(n1),
+                                        dx_add=None if first else d_a, keep_splits=True, wgrad_to=t._wg(n1, t.bn_scale[n1]), low_res=lr,
+                                        out_mask=x_in if (can_mask and stride == 1) else None)
+                d_x = None if first else d_s
+                masked = can_mask and stride == 1
+                if lr and not first:
+                    d_x = T.strided_scatter(d_s, tuple(x_in.shape), stride, mask=x_in if can_mask else None)
+                    masked = can_mask
+            else:
+                # identity shortcut: d x_in = g_y1 W1 + g_out; x_in is the previous unit's ReLU output, so its mask can ride in this GEMM's
+                # epilogue -- unless that output has a second consumer whose gradient must be added before the mask (inject)
+                can_mask = t.mask_epilogue and prev_nm is not None and inject.get(prev_nm) is None
+                d_x, dw = T.conv1x1_bwd(x_in, t.w(na), g_y1, dx_add=g_out, w_t=t.wt(na), keep_splits=True, wgrad_to=t._wg(na, t.bn_scale[na]),
+                                        out_mask=x_in if can_mask else None)
+                masked = can_mask
+        t._bucket_ready(prev_bucket)
+
+    # ---- FPN neck --------------------------------------------------------------------------------------------
+    def neck_forward(self, ends):
+        """ends {2, 3, 4, 5: stage output} -> (feats {4, 8, 16, 32: pyramid map}, the context of `neck_backward`: lateral inputs and tops)."""
+        t = self.t
+        src = {32: ends[5], 16: ends[4], 8: ends[3], 4: ends[2]}
+        if t.trunk_fp32:             # float32 trunk (parity tests): bf16 copies for the bf16 neck / heads
+            src = {k: v.to(torch.bfloat16) for k, v in src.items()}
+        tops, feats = fpn_neck(t._conv, ops.upsample2x_add_, src[32], {4: src[16], 3: src[8], 2: src[4]})
+        return feats, (src, tops)
+
+    def neck_backward(self, ctx, d_feats):
+        """d_feats {4, 8, 16, 32: gradient of the pyramid map}: the top-down pathway reversed, finest level first, gradients flowing up to the
+        coarser tops.  -> (gradient of conv5, inject = {'4b22', '3b3': gradient of that unit's output} for `backward`; res2c is frozen)."""
+        t = self.t
+        src, tops = ctx
+        bt = torch.bfloat16
+        d_tops, inject, d_c5 = {}, {}, None
+        for lvl in (4, 8, 16, 32):
+            n3, n1 = 'fpn_ft%d_3x3' % lvl, 'fpn_ft%d_1x1' % lvl
+            d_top, dw = T.conv3x3_bwd(tops[lvl], self._dgrad_w(n3, 256), d_feats[lvl], dil=1, keep_splits=True, wgrad_to=t._wg(n3))
+            T.colsum_add(d_feats[lvl], *t._bg(n3))             # (bias gradients: the bucket's grouped column-sum launch)
+            if lvl in d_tops:                                    # + the gradient that came down from the finer level (fp32 block sums)
+                d_top = torch.add(d_top, d_tops[lvl]).to(bt)
+            if lvl < 32:       # tops[lvl] = lateral + up2x(tops[2 lvl]): adjoint of nearest upsampling = 2x2 block sums (fp32 accumulation, read as bf16)
+                Bh, Hh, Wh, Ch = d_top.shape
+                d_tops[lvl * 2] = d_top.view(Bh, Hh // 2, 2, Wh // 2, 2, Ch).sum((2, 4), dtype=torch.float32)
+            d_top = d_top.contiguous()
+            d_src, dw = T.conv1x1_bwd(src[lvl], t.w(n1), d_top, need_dx=(lvl != 4), w_t=t.wt(n1), keep_splits=True, wgrad_to=t._wg(n1))   # res2c is frozen
+            T.colsum_add(d_top, *t._bg(n1))
+            if lvl == 32:
+                d_c5 = d_src
+            elif lvl == 16:
+                inject['4b22'] = d_src
+            elif lvl == 8:
+                inject['3b3'] = d_src
+        if t.trunk_fp32:
+            d_c5, inject = d_c5.float(), {k: v.float() for k, v in inject.items()}
+        return d_c5, inject
+
+    # ---- RPN head --------------------------------------------------------------------------------------------
+    def rpn_forward(self, conv4):
+        """-> (r, rpn [B,h,w,2A | 4A] float32): backbone.rpn_head on the trainer's weights."""
+        return rpn_head(self.t._conv, conv4)
+
+    def rpn_backward(self, conv4, r, d_rpn):
+        """RPN head backward (joins the trunk at conv4), and with it the two RPN weight gradients as their own grouped launch on
+        RPN_WGRAD_WORKGROUPS workgroups.  -> dict(g_r, d_conv4_rpn, rq_keep: what that launch reads, to be kept alive by the caller)."""
+        t = self.t
+        rq = ops.WgradQueue(deterministic=t.deterministic)
+        wg = lambda n: t._wg(n)[:2] + (rq,)
+        g_r, dw = T.conv1x1_bwd(r, t.w('rpn_out'), d_rpn, w_t=t.wt('rpn_out'), keep_splits=True, wgrad_to=wg('rpn_out'), relu_mask=r)
+        T.colsum_add(d_rpn, *t._bg('rpn_out'))
+        d_conv4_rpn, dw = T.conv3x3_bwd(conv4, self._dgrad_w('rpn_conv_3x3', 512), g_r, dil=1, keep_splits=True, wgrad_to=wg('rpn_conv_3x3'))
+        T.colsum_add(g_r, *t._bg('rpn_conv_3x3'))
+        return dict(g_r=g_r, d_conv4_rpn=d_conv4_rpn, rq_keep=rq.flush(workgroups=RPN_WGRAD_WORKGROUPS))

@@ -26,7 +26,7 @@ import torch
 
 from . import ops, losses, train_ops as T
 from . import dist as D
-from .backbone import unit_names, conv_bn_names, fold_bn, EPS
+from .backbone import unit_names, conv_bn_names, fold_bn, EPS, TrunkTrain
 from .relation import BoxHeadTrain
 from .detector import Config, fc1_channels_last_perm
 from .learn_nms import LearnNMSTrain, rank_embedding
@@ -57,12 +57,6 @@ class TrainConfig(Config):
                                   # backward, bias-gradient column sums, loss scalars, the geometry backward, the learn-NMS take adjoint, the
                                   # stream-K weight-gradient flush) runs its ordered form -- two steps from the same state give the same bits
                                   # (DESIGN.md section 9).  C4 graphs with ROIPooling only: dcn, roi_align and FPNTrainer are refused
-
-
-# workgroups of the RPN head's grouped weight-gradient launch on the side stream: a quarter of the chip, the head's kernels beside it keep
-# theirs (same box, 8 images: 16.99 ms per step with these products in the heads bucket's launch on the main stream, 16.92 on 32 workgroups,
-# 16.87 - 16.89 on 64, 16.99 on 128)
-RPN_WGRAD_WORKGROUPS = 64
 
 
 def conv4_hw(h, w):
@@ -375,25 +369,8 @@ class Trainer(object):
                 group = ('rel_cat_' + i, 0 if name.startswith('qk_') else self.W.slices['qk_' + i][1][0])
             self._relayout.add(name, self.w(name), taps=taps, pad_co=1 if taps == 9 else 64, group=group)
         self._relayout.build()
-        # ---- res3 .. res5 block boundaries on the inference chain kernels (csrc/bottleneck.hip): expand + shortcut + ReLU of unit u
-        # and reduce + ReLU of unit u + 1 in one launch.  They read the weights in MFMA-fragment order; the trained weights change every
-        # step, so ONE grouped launch per step (ops.FragRepack) rewrites those copies next to the data-gradient layouts above.
-        # (The float32 trunk keeps the per-layer convolution launches.)
-        self._fragpack = ops.FragRepack(dev)
-        self.chain_units = {}                               # unit -> (has_next_reduce, next unit)
-        if not self.trunk_fp32:
-            trainable = [u for u in self.units if u[0] >= 3]
-            for (st, nm, ic, mc, oc, stride, dil, proj), nxt in zip(trainable, trainable[1:] + [None]):
-                if c.dcn and st == 5:
-                    continue
-                with_reduce = nxt is not None and nxt[0] == st and not nxt[7] and mc in ops.CHAIN_MIDS
-                if not with_reduce and mc not in ops.CHAIN_EXPAND_MIDS:
-                    continue
-                self._fragpack.add('w3:' + nm, self.w('res%s_branch2c' % nm), 0)
-                if with_reduce:
-                    self._fragpack.add('w1:' + nxt[1], self.w('res%s_branch2a' % nxt[1]), 1)
-                self.chain_units[nm] = (with_reduce, nxt[1] if with_reduce else None)
-            self._fragpack.build()
+        # ---- res3 .. res5, FPN neck, RPN head convolutions and their adjoints (registers the chain kernels' weight copies: _fragpack, chain_units)
+        self._trunk = TrunkTrain(self)
         # data gradient through `relu(expand + shortcut)` with the ReLU mask in the GEMM epilogue (relnet_gemm_nt_mask) instead of a
         # separate relnet_relu_bwd pass over three [pixels, 4 mid] maps per unit (off for the float32 trunk)
         self.mask_epilogue = not self.trunk_fp32
@@ -464,56 +441,17 @@ class Trainer(object):
         return self.Bv.view(self.Bv.grad, name).view(-1), self._cq
 
     # ---- forward -------------------------------------------------------------------------------------------
-    def _conv(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None, bias=None, out_dtype=None):
-        bias = self.conv_bias[name] if bias is None else bias
+    def _conv(self, x, name, stride=1, pad=0, dil=1, relu=False, resid=None, out_dtype=None):
+        """Layer `name` on the working weights; its bias is the folded BatchNorm's frozen one (res3 .. res5) or the layer's own trainable one."""
+        bias = self.conv_bias[name] if name in self.conv_bias else self.b(name)
         return ops.conv2d_nhwc(x, self.w(name), bias, ksize=self.ksize.get(name, 1), stride=stride, pad=pad, dil=dil, relu=relu,
                                resid=resid, out_dtype=out_dtype)
 
     def _trunk_forward(self, data, at_conv4=None, im_info=None):
-        """Frozen stem + res2, then res3..res5 keeping every ReLU output.  Returns (conv5, conv4, saved units, stage ends).
-        at_conv4(conv4): called once conv4 exists, before res5 is queued (the RPN branch forks there).  data: float NCHW or uint8
-        [B,H,W,3] BGR HWC (Backbone.forward; im_info gives each image's extent)."""
-        c = self.cfg
-        x = self._frozen_backbone.forward_res2(data, im_info)      # (float32 NHWC for the float32 trunk: Backbone impl 'hip32')
-        saved = []
-        conv4 = None
-        ends = {}
-        y_pre = None               # reduce output of the coming unit when the previous unit's chain kernel already produced it
-        for stage, nm, ic, mc, oc, stride, dil, proj in self.units:
-            n1, na, nb, nc = 'res%s_branch1' % nm, 'res%s_branch2a' % nm, 'res%s_branch2b' % nm, 'res%s_branch2c' % nm
-            if stage == 5 and conv4 is None:
-                conv4 = x
-                if at_conv4 is not None:
-                    at_conv4(conv4)
-            if proj and stage > 2:
-                ends[stage - 1] = x
-            if stage == 2:
-                continue                   # (ran inside forward_res2)
-            sc = self._conv(x, n1, stride=stride) if proj else x
-            y1 = y_pre if y_pre is not None else self._conv(x, na, stride=stride, relu=True)
-            y_pre = None
-            off = None
-            if c.dcn and stage == 5:       # 72-channel offset conv -> DeformableConvolution(num_deformable_group=4) + BN + ReLU
-                off = self._conv(y1, nb + '_offset', pad=2, dil=2, bias=self.b(nb + '_offset'), out_dtype=torch.float32)
-                y2, col = ops.deformable_conv(y1.permute(0, 3, 1, 2), off.permute(0, 3, 1, 2), self.w(nb), self.conv_bias[nb],
-                                              3, 1, 2, 2, 4, relu=True, want_col=True)
-                y2 = y2.permute(0, 2, 3, 1)
-                off = (off, col)           # (the sampled column matrix rides along to the backward: the weight gradient's X operand)
-            else:
-                y2 = self._conv(y1, nb, pad=dil, dil=dil, relu=True)
-            ch = self.chain_units.get(nm)
-            if ch is not None and ops.chain_worthwhile(y2.numel() // y2.shape[-1], mc):
-                # expand + shortcut + ReLU and (inside a stage) the NEXT unit's reduce + ReLU in one pixel-wise kernel; every activation
-                # the backward needs (x_next, mid1_next) is still written, nothing is overwritten in place
-                w1f = self._fragpack.get('w1:' + ch[1]) if ch[0] else None
-                b1 = self.conv_bias['res%s_branch2a' % ch[1]] if ch[0] else None
-                out, y_pre = ops.bottleneck_chain(y2, sc.contiguous(), self._fragpack.get('w3:' + nm), w1f, self.conv_bias[nc], b1)
-            else:
-                out = self._conv(y2, nc, relu=True, resid=sc)
-            saved.append((stage, nm, stride, dil, proj, x, y1, y2, out, off))
-            x = out
-        ends[5] = x
-        return x, conv4, saved, ends
+        return self._trunk.forward(data, at_conv4, im_info)
+
+    def _trunk_backward(self, saved, d_x, inject):
+        return self._trunk.backward(saved, d_x, inject)
 
     def rpn_targets(self, gt_boxes, num_gt, im_info, feat_hw):
         """lib/rpn/rpn.py:80-244 (`assign_anchor`, host numpy inside the reference's AnchorLoader) on the device for the whole
@@ -582,8 +520,7 @@ class Trainer(object):
                 early = self.rpn_targets(gt_boxes, num_gt, im_info, conv4_hw(*ops.image_hw(data)))
 
         def rpn_branch(conv4):
-            r = self._conv(conv4, 'rpn_conv_3x3', pad=1, relu=True, bias=self.b('rpn_conv_3x3'))
-            rpn = self._conv(r, 'rpn_out', bias=self.b('rpn_out'), out_dtype=torch.float32)             # [B,h,w,72]
+            r, rpn = self._trunk.rpn_forward(conv4)                                                      # [B,h,w,72]
             h, wd_ = rpn.shape[1], rpn.shape[2]
             na2 = self.na2
             lbl, tgt_in, wgt_in = (rpn_label, rpn_bbox_target, rpn_bbox_weight) if early is None else early
@@ -626,17 +563,6 @@ class Trainer(object):
                 br.update(rpn_cls_prob=rpn_prob, rpn_label=lbl, rpn_bbox_loss_map=rpn_l1)
                 out['rpn_cls_prob'], out['rpn_label'], out['rpn_bbox_loss_map'] = rpn_prob, lbl, rpn_l1
 
-        def rpn_backward(conv4, r, d_rpn):
-            # RPN head backward (joins the trunk at conv4), on the side stream beside ROI pooling / the 2FC head / the learn-NMS branch (launches of
-            # <= 150 workgroups), and with it the two RPN weight gradients as their own grouped launch on RPN_WGRAD_WORKGROUPS workgroups
-            rq = ops.WgradQueue(deterministic=self.deterministic)
-            wg = lambda n: self._wg(n)[:2] + (rq,)
-            g_r, dw = T.conv1x1_bwd(r, self.w('rpn_out'), d_rpn, w_t=self.wt('rpn_out'), keep_splits=True, wgrad_to=wg('rpn_out'), relu_mask=r)
-            T.colsum_add(d_rpn, *self._bg('rpn_out'))
-            d_conv4_rpn, dw = T.conv3x3_bwd(conv4, self._dgrad_w('rpn_conv_3x3', 512), g_r, dil=1, keep_splits=True, wgrad_to=wg('rpn_conv_3x3'))
-            T.colsum_add(g_r, *self._bg('rpn_conv_3x3'))
-            br.update(g_r=g_r, d_conv4_rpn=d_conv4_rpn, rq_keep=rq.flush(workgroups=RPN_WGRAD_WORKGROUPS))
-
         def fork(conv4):
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -644,15 +570,15 @@ class Trainer(object):
         conv5, conv4, saved, _ = self._trunk_forward(data, at_conv4=fork, im_info=im_info)
         # (a float32 trunk -- cfg.trunk_fp32, parity tests -- hands bf16 copies to the bf16 heads and takes their gradients back as float32)
         conv5, conv4 = conv5.to(torch.bfloat16), conv4.to(torch.bfloat16)
-        feat = self._conv(conv5, 'conv_new_1', relu=True, bias=self.b('conv_new_1'))
+        feat = self._conv(conv5, 'conv_new_1', relu=True)
         # W^T / tap-flipped copies of the current weights for every data-gradient product: only the BACKWARD reads them, so they are made
         # here, where the main stream otherwise waits for the proposals (one image: the RPN branch's single-workgroup sort / NMS kernels
         # are the longer path and leave the chip idle)
         self._relayout.run()
         if rpn_bwd_side:
             side.wait_stream(main)
-            with torch.cuda.stream(side):
-                rpn_backward(*br.pop('bwd'))
+            with torch.cuda.stream(side):       # beside ROI pooling / the 2FC head / the learn-NMS branch (launches of <= 150 workgroups)
+                br.update(self._trunk.rpn_backward(*br.pop('bwd')))
             main.wait_event(br['ev'])
         else:
             main.wait_stream(side)
@@ -696,88 +622,6 @@ class Trainer(object):
         out['cls_score'] = cls_score
         return out
 
-    def _trunk_backward(self, saved, d_x, inject):
-        """res5 -> res3 backward.  d_x = gradient of the last unit's output; inject[unit] = extra gradient of that unit's output."""
-        B = saved[0][5].shape[0]
-        bt = torch.bfloat16
-        # trunk: res5 -> res3.  Gradient buckets are announced as they complete (heads first; with DCN the res5 offset
-        # convolutions live in the heads bucket, which is then complete only after res5): dist.BucketedAllReduce overlaps
-        # each bucket's all-reduce with the rest of the backward pass
-        dcn = self.cfg.dcn
-        self._grad_buckets()
-        if not dcn:
-            self._bucket_ready('heads')
-        prev_bucket = None
-        masked = False            # d_x already carries the ReLU mask of the unit's output (relnet_gemm_nt_mask of the unit after it)
-        order = list(reversed(saved))
-        for pos, (stage, nm, stride, dil, proj, x_in, y1, y2, o, off) in enumerate(order):
-            bucket = self._unit_bucket[nm]
-            if prev_bucket is not None and bucket != prev_bucket:
-                if dcn and prev_bucket == 'res5':
-                    self._bucket_ready('res5', 'heads')        # both complete at this point: one cut, two collectives
-                else:
-                    self._bucket_ready(prev_bucket)
-            prev_bucket = bucket
-            n1, na, nb, nc_ = 'res%s_branch1' % nm, 'res%s_branch2a' % nm, 'res%s_branch2b' % nm, 'res%s_branch2c' % nm
-            if inject.get(nm) is not None:       # a second consumer of this unit's output (RPN head at conv4, FPN laterals)
-                assert not masked
-                d_x = inject[nm] if d_x is None else d_x + inject[nm]
-            g_out = d_x if masked else T.relu_bwd(d_x, o)
-            masked = False
-            # (ReLU masks of the two inner activations ride in the data-gradient kernels' epilogues)
-            g_y2, dw = T.conv1x1_bwd(y2, self.w(nc_), g_out, w_t=self.wt(nc_), keep_splits=True, wgrad_to=self._wg(nc_, self.bn_scale[nc_]), relu_mask=y2)
-            if off is not None:            # deformable branch2b: data + offset gradients, then the offset conv's own backward
-                off, col = off
-                gd, goff, dw = ops.deformable_conv_bwd(y1.permute(0, 3, 1, 2), off.permute(0, 3, 1, 2), self.w(nb),
-                                                       g_y2.permute(0, 3, 1, 2), 3, 1, 2, 2, 4, col=col)
-                self._add_wgrad(nb, dw, self.bn_scale[nb])
-                no = nb + '_offset'
-                goff_p = torch.zeros((B, off.shape[1], off.shape[2], 128), device=off.device, dtype=bt)   # 72 -> 128 channels
-                goff_p[..., :72] = goff
-                wd_ = self.w(no).view(72, 3, 3, -1).flip(1, 2).permute(3, 1, 2, 0)                     # [Cin,3,3,72]
-                wdp = torch.zeros((wd_.shape[0], 3, 3, 128), device=off.device, dtype=bt); wdp[..., :72] = wd_
-                d_off_in, dwo = T.conv3x3_bwd(y1, wdp.reshape(wd_.shape[0], -1).contiguous(), goff_p, dil=2, keep_splits=True)
-                self._add_wgrad(no, dwo.sum(0)[:72]); self._add_bgrad(no, goff.sum((0, 1, 2)))
-                d_y1 = (gd + d_off_in.float()).to(bt).contiguous()
-            else:
-                g_y1, dw = T.conv3x3_bwd(y1, self._dgrad_w(nb, y2.shape[3]), g_y2, dil=dil, keep_splits=True, wgrad_to=self._wg(nb, self.bn_scale[nb]),
-                                         relu_mask=y1)
-            if off is not None:
-                g_y1 = T.relu_bwd(d_y1, y1)
-            first = (stage == 3 and proj)         # res3a: its input comes from the frozen res2 -> no data gradient
-            if proj:
-                # both branches read the same (sampled) input: their data gradients are summed in the second GEMM's epilogue -- at the SAMPLED
-                # resolution for a stride-2 unit, then scattered to the input's resolution once, with the previous unit's ReLU mask in the same
-                # pass when that output has no other consumer (was: 2 zero fills + 2 strided copies + a full-resolution add + relu_bwd)
-                prev_nm = order[pos + 1][1] if pos + 1 < len(order) else None
-                lr = stride != 1
-                # a second consumer's gradient of this unit's INPUT (the RPN head at conv4, in front of the stride-1 res5a) rides in the first
-                # GEMM's epilogue; the input's ReLU mask can then ride in the second one's
-                inj = inject.get(prev_nm) if (stride == 1 and not first and prev_nm is not None) else None
-                fold = inj is not None and inj.dtype == g_y1.dtype and tuple(inj.shape) == tuple(x_in.shape) and inj.is_contiguous()
-                d_a, dw = T.conv1x1_bwd(x_in, self.w(na), g_y1, stride=stride, need_dx=not first, w_t=self.wt(na), keep_splits=True, wgrad_to=self._wg(na, self.bn_scale[na]),
-                                        dx_add=inj if fold else None, low_res=lr)
-                if fold:
-                    inject = {k: v for k, v in inject.items() if k != prev_nm}
-                can_mask = self.mask_epilogue and not first and prev_nm is not None and inject.get(prev_nm) is None
-                d_s, dw = T.conv1x1_bwd(x_in, self.w(n1), g_out, stride=stride, need_dx=not first, w_t=self.wt(n1),
-                                        dx_add=None if first else d_a, keep_splits=True, wgrad_to=self._wg(n1, self.bn_scale[n1]), low_res=lr,
-                                        out_mask=x_in if (can_mask and stride == 1) else None)
-                d_x = None if first else d_s
-                masked = can_mask and stride == 1
-                if lr and not first:
-                    d_x = T.strided_scatter(d_s, tuple(x_in.shape), stride, mask=x_in if can_mask else None)
-                    masked = can_mask
-            else:
-                # identity shortcut: d x_in = g_y1 W1 + g_out; x_in is the previous unit's ReLU output, so its mask can ride in this GEMM's
-                # epilogue -- unless that output has a second consumer whose gradient must be added before the mask (inject)
-                prev_nm = order[pos + 1][1] if pos + 1 < len(order) else None
-                can_mask = self.mask_epilogue and prev_nm is not None and inject.get(prev_nm) is None
-                d_x, dw = T.conv1x1_bwd(x_in, self.w(na), g_y1, dx_add=g_out, w_t=self.wt(na), keep_splits=True, wgrad_to=self._wg(na, self.bn_scale[na]),
-                                        out_mask=x_in if can_mask else None)
-                masked = can_mask
-        self._bucket_ready(prev_bucket)
-
     def _head_forward_backward(self, pooled2, rois_t, N, label, bbox_target, bbox_weight, im_info, gt_boxes, num_gt, out,
                                key_count=None):
         """2FC head + relation modules + OHEM + losses (+ learn-NMS branch) and their adjoint down to the pooled features.
@@ -819,15 +663,6 @@ class Trainer(object):
     def _lnms_forward_backward(self, cls_score, bbox_pred, rois, im_info, feat, gt_boxes, num_gt, n_valid=None, d_cls_out=None):
         """Train branch of the learn-NMS head and its adjoint: learn_nms.LearnNMSTrain.__call__ (arguments and return values there)."""
         return self._lnms(cls_score, bbox_pred, rois, im_info, feat, gt_boxes, num_gt, n_valid=n_valid, d_cls_out=d_cls_out)
-
-    def _dgrad_w(self, name, cout):
-        """[Cout, 9*Cin] packed forward weights -> [Cin, 9*Cout] tap-flipped data-gradient weights."""
-        wt = self.wt(name)
-        if wt is not None:
-            return wt
-        w = self.w(name)
-        cin = w.shape[1] // 9
-        return w.view(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).reshape(cin, 9 * cout).contiguous()
 
     # ---- checkpoint view -----------------------------------------------------------------------------------
     def export_params(self):
@@ -1194,7 +1029,6 @@ class FPNTrainer(Trainer):
         the level dispatch, no relation keys (key_count), never ranked by the learn-NMS branch."""
         c = self.cfg
         B, N = proposals.shape[:2]
-        bt = torch.bfloat16
         if any(n % 32 for n in ops.image_hw(data)):
             raise ValueError("FPN images must be padded to IMAGE_STRIDE 32, got %s" % (tuple(data.shape),))
         self._grad_buckets().reset()
@@ -1203,14 +1037,7 @@ class FPNTrainer(Trainer):
         self._fragpack.run()            # ... and the fragment-order copies the chain kernels of the forward read
         out = {}
         conv5, conv4, saved, ends = self._trunk_forward(data, im_info=im_info)
-        # ---- neck: 1x1 laterals (+bias), nearest 2x upsampling + sum, 3x3 output convs
-        src = {32: ends[5], 16: ends[4], 8: ends[3], 4: ends[2]}
-        if self.trunk_fp32:             # float32 trunk (parity tests): bf16 copies for the bf16 neck / heads
-            src = {k: v.to(bt) for k, v in src.items()}
-        tops = {32: self._conv(src[32], 'fpn_ft32_1x1', bias=self.b('fpn_ft32_1x1'))}
-        for lvl in (16, 8, 4):
-            tops[lvl] = ops.upsample2x_add_(self._conv(src[lvl], 'fpn_ft%d_1x1' % lvl, bias=self.b('fpn_ft%d_1x1' % lvl)), tops[lvl * 2])
-        feats = {lvl: self._conv(tops[lvl], 'fpn_ft%d_3x3' % lvl, pad=1, bias=self.b('fpn_ft%d_3x3' % lvl)) for lvl in (4, 8, 16, 32)}
+        feats, neck_ctx = self._trunk.neck_forward(ends)      # 1x1 laterals (+bias), nearest 2x upsampling + sum, 3x3 output convs
         # ---- rois: labels / targets, then level dispatch (non-gt rows first, gt rows after)
         rois5 = torch.cat([torch.zeros((B, N, 1), device=proposals.device), proposals], 2)
         rois5[:, :, 0] = torch.arange(B, device=proposals.device, dtype=torch.float32).view(B, 1)
@@ -1241,28 +1068,7 @@ class FPNTrainer(Trainer):
         x2, f1, cls_score, bbox_pred, labels_ohem, weights_ohem = hs
         # ---- pooling backward into the four pyramid maps
         d_feats = dict(zip((4, 8, 16, 32), self.pool.backward(d_pool, pool_ctx)))
-        # ---- neck backward (top-down pathway reversed: finest level first, gradients flow up to the coarser tops)
-        d_tops, inject, d_c5 = {}, {}, None
-        for lvl in (4, 8, 16, 32):
-            n3, n1 = 'fpn_ft%d_3x3' % lvl, 'fpn_ft%d_1x1' % lvl
-            d_top, dw = T.conv3x3_bwd(tops[lvl], self._dgrad_w(n3, 256), d_feats[lvl], dil=1, keep_splits=True, wgrad_to=self._wg(n3))
-            T.colsum_add(d_feats[lvl], *self._bg(n3))             # (bias gradients: the bucket's grouped column-sum launch)
-            if lvl in d_tops:                                    # + the gradient that came down from the finer level (fp32 block sums)
-                d_top = torch.add(d_top, d_tops[lvl]).to(bt)
-            if lvl < 32:       # tops[lvl] = lateral + up2x(tops[2 lvl]): adjoint of nearest upsampling = 2x2 block sums (fp32 accumulation, read as bf16)
-                Bh, Hh, Wh, Ch = d_top.shape
-                d_tops[lvl * 2] = d_top.view(Bh, Hh // 2, 2, Wh // 2, 2, Ch).sum((2, 4), dtype=torch.float32)
-            d_top = d_top.contiguous()
-            d_src, dw = T.conv1x1_bwd(src[lvl], self.w(n1), d_top, need_dx=(lvl != 4), w_t=self.wt(n1), keep_splits=True, wgrad_to=self._wg(n1))   # res2c is frozen
-            T.colsum_add(d_top, *self._bg(n1))
-            if lvl == 32:
-                d_c5 = d_src
-            elif lvl == 16:
-                inject['4b22'] = d_src
-            elif lvl == 8:
-                inject['3b3'] = d_src
-        if self.trunk_fp32:
-            d_c5, inject = d_c5.float(), {k: v.float() for k, v in inject.items()}
+        d_c5, inject = self._trunk.neck_backward(neck_ctx, d_feats)
         self._trunk_backward(saved, d_c5, inject)
         out.update(rois=rois_s, perm=perm, roi_level=level, label=labels_ohem, bbox_target=bbox_target, bbox_weight=weights_ohem,
                    bbox_pred=bbox_pred, cls_score=cls_score)

@@ -88,6 +88,45 @@ def test_trainer_holds_no_box_head_code():
     assert 'BoxHeadTrain' in imported and '_head_forward_backward' in defined
 
 
+def test_trainer_holds_no_trunk_code():
+    """The unit walk, the bottleneck unit, the FPN neck and the RPN head convolutions are written once, in backbone.py, with their adjoints
+    in backbone.TrunkTrain: train.py names no trunk or neck layer outside construction / export / checkpoint / bucket code, calls none of the
+    trunk's kernels, and keeps _trunk_forward / _trunk_backward as delegates.  In backbone.py each of the two layer names stands in ONE
+    forward function (besides __init__ and TrunkTrain's adjoints, neck_backward / rpn_backward, which must name the layers they differentiate)."""
+    import ast
+    pkg = os.path.join(ROOT, 'relation-networks-for-object-detection_amd')
+
+    def strings_by_function(path):
+        """[(name of the outermost enclosing function or method, string constant)]"""
+        found = []
+
+        def visit(node, owner):
+            for child in ast.iter_child_nodes(node):
+                inner = owner
+                if owner is None and isinstance(child, (ast.FunctionDef, ast.Lambda)):
+                    inner = getattr(child, 'name', '<lambda>')
+                if isinstance(child, ast.Constant) and isinstance(child.value, str):
+                    found.append((owner, child.value))
+                visit(child, inner)
+        visit(ast.parse(open(path).read(), path), None)
+        return found
+
+    train = os.path.join(pkg, 'train.py')
+    allowed = {'__init__', 'export_params', 'checkpoint_params', 'save_checkpoint', '_grad_buckets', '_bucket_ready'}
+    bad = [(f, s) for f, s in strings_by_function(train) if s.startswith(('res%s_branch', 'fpn_ft%d')) and f not in allowed]
+    assert not bad, bad
+    tree = ast.parse(open(train).read(), train)
+    called = {n.func.attr for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute)
+              and isinstance(n.func.value, ast.Name) and n.func.value.id == 'ops'}
+    assert not called & {'bottleneck_chain', 'deformable_conv', 'deformable_conv_bwd', 'upsample2x_add_'}, called
+    defined = {n.name for n in ast.walk(tree) if isinstance(n, ast.FunctionDef)}
+    assert {'_trunk_forward', '_trunk_backward'} <= defined
+    in_backbone = strings_by_function(os.path.join(pkg, 'backbone.py'))
+    for layer, adjoint in (('fpn_ft%d_1x1', 'neck_backward'), ('rpn_out', 'rpn_backward')):
+        owners = {f for f, s in in_backbone if s == layer and f is not None} - {'__init__', adjoint}
+        assert len(owners) == 1, (layer, owners)
+
+
 def test_proposal_prop_protocol():
     import relnet_amd  # noqa: F401
     from relnet_amd import operator_py
