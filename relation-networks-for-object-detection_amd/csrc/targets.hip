@@ -663,9 +663,10 @@ extern "C" int relnet_proposal_target_ex(const float* rois, const float* gt, con
                                          float* label, float* bbox_target, float* bbox_weight, int B, int N, int Gmax,
                                          int num_reg, int class_agnostic, float bg_thresh_hi, const double* means4,
                                          const double* stds4, const double* weights4, const int* num_rois, void* stream) {
-  RELNET_REQUIRE(rois && gt && num_gt && rois_out && label && bbox_target && bbox_weight && means4 && stds4 && weights4,
-                 "relnet_proposal_target: null operand");
   RELNET_REQUIRE(B > 0 && N >= 0 && Gmax >= 0 && N + Gmax > 0 && num_reg > 0, "relnet_proposal_target: bad shape");
+  // (an empty operand has no address: N = 0 is the appended gt rows alone, Gmax = 0 the proposals alone, and neither is read then)
+  RELNET_REQUIRE((rois || N == 0) && (gt || Gmax == 0) && num_gt && rois_out && label && bbox_target && bbox_weight && means4 && stds4 && weights4,
+                 "relnet_proposal_target: null operand");
   PTArgs g{rois, gt, num_gt, rois_out, label, bbox_target, bbox_weight, N, Gmax, num_reg, class_agnostic, bg_thresh_hi,
            {means4[0], means4[1], means4[2], means4[3]}, {stds4[0], stds4[1], stds4[2], stds4[3]},
            {weights4[0], weights4[1], weights4[2], weights4[3]}, num_rois};
