@@ -92,6 +92,28 @@ int relnet_roi_align_levels_bwd(const void* grad_out, const long* out_strides4, 
                                 const float* spatial_scales, int num_levels, int R, int B, int C, int PH, int PW, int sampling_ratio,
                                 int aligned, int batch_index_base, int dtype, void* stream);
 
+/* ---- mx.contrib.sym.PSROIPooling(data, rois, spatial_scale, output_dim, pooled_size, group_size): `_contrib_PSROIPooling` of
+ * relation_rcnn/operator_cxx, psroi_pooling.cu:32-101 (forward) and :132-194 (backward), parameters psroi_pooling-inl.h:36-46.
+ * data logical [B, C, H, W] with C == output_dim * group_size^2, fp32 or bf16 (dtype), element strides (b, c, y, x): NCHW or channels-last;
+ * rois [R, 5] fp32; out logical [R, output_dim, P, P] (P = pooled_size) in data's dtype with element strides (r, c, ph, pw);
+ * mapping_channel (or NULL): fp32 with out's strides, the input channel c = (ctop g + gh) g + gw of each bin, the operator's second output.
+ * Arithmetic in fp32, every product and sum rounded on its own (no FMA): start = roundf(x1) scale, end = (roundf(x2) + 1) scale (halves
+ * away from zero), extent = max(end - start, 0.1), bins [floor(p bin + start), ceil((p + 1) bin + start)) clipped to the map; an empty bin
+ * gives 0.  A roi whose batch index minus batch_index_base is outside [0, B) pools to zeros and contributes no gradient (tested before
+ * any address is formed).  R == 0 is valid.  Every extent is folded into grid.x: no limit below 2^31 - 1 workgroups of 256 elements.
+ * SUMMATION ORDER.  Forward: each output element is the fp32 sum from 0 of its window's cells, h ascending then w ascending, divided
+ * once (IEEE fp32) by the cell count; a bf16 output is rounded once, last.  Backward (gather form, no float atomics): each word of grad_in
+ * (fp32, element strides (b, c, y, x), NCHW or NHWC memory) is the fp32 sum from 0, in ascending (roi, ph, pw) order, of
+ * grad_out[n][ctop][ph][pw] / bin_area (one IEEE fp32 division each; grad_out fp32 or bf16 by dtype) over the bins that hold the cell and
+ * map to the channel; accumulate == 0 WRITES that sum (no zero fill needed; R == 0 writes zeros), accumulate != 0 (kAddTo) adds it to the
+ * old value with one addition.  Neither order depends on the grid, the CU count, the layout or the alignment of an operand.          */
+int relnet_psroi_pool_fwd(const void* data, const long* data_strides4, const float* rois /*[R,5]*/, void* out, const long* out_strides4,
+                          float* mapping_channel /*or NULL*/, int R, int B, int C, int H, int W, int output_dim, int pooled_size,
+                          int group_size, float spatial_scale, int batch_index_base, int dtype, void* stream);
+int relnet_psroi_pool_bwd(const void* grad_out, const long* out_strides4, const float* rois, float* grad_in,
+                          const long* grad_in_strides4, int R, int B, int C, int H, int W, int output_dim, int pooled_size,
+                          int group_size, float spatial_scale, int batch_index_base, int accumulate, int dtype, void* stream);
+
 /* ---- mx.symbol.ROIPooling(pooled_size=(7,7), spatial_scale=1/16), SYM_REL:252-253 ---------------
  * data/out described by element strides (b|r, c, y, x) so NCHW and channels-last both work.       */
 int relnet_roi_pool_fwd(const void* data, const long* data_strides4, const float* rois /*[R,5]*/, void* out,

@@ -3,6 +3,8 @@
 // The reference registers two legacy MXNet operators for its DCN configuration
 //   _contrib_DeformableConvolution     relation_rcnn/operator_cxx/deformable_convolution-inl.h:39-470
 //   _contrib_DeformablePSROIPooling    relation_rcnn/operator_cxx/deformable_psroi_pooling-inl.h:32-270
+// and the directory's third operator
+//   _contrib_PSROIPooling              relation_rcnn/operator_cxx/psroi_pooling-inl.h:33-231
 // as `XParam` (dmlc parameter struct) + `XProp : OperatorProperty` + `XOp : Operator`.  This header restates that
 // shape -- the same class and method names, argument order, blob indices (conv::kData ...), OpReqType semantics and
 // CHECK conditions -- without MXNet / mshadow / dmlc, so that an MXNet build can forward its operator bodies to
@@ -53,6 +55,7 @@ inline void relnet_hipcheck(hipError_t e) { if (e != hipSuccess) throw std::runt
 
 namespace conv { enum { kData = 0, kOffset = 1, kWeight = 2, kBias = 3, kOut = 0 }; }
 namespace deformablepsroipool { enum { kData = 0, kBox = 1, kTrans = 2, kOut = 0, kTopCount = 1 }; }
+namespace psroipool { enum { kData = 0, kBox = 1, kOut = 0, kMappingChannel = 1 }; }
 
 // ------------------------------------------------------------------------------------------------------------------
 struct DeformableConvolutionParam {             // deformable_convolution-inl.h:39-76
@@ -371,6 +374,104 @@ class DeformablePSROIPoolingProp {                 // deformable_psroi_pooling-i
 
  private:
   DeformablePSROIPoolingParam param_;
+};
+
+// ------------------------------------------------------------------------------------------------------------------
+struct PSROIPoolingParam {                      // psroi_pooling-inl.h:33-47
+  float spatial_scale = 0.f;
+  int output_dim = 0, pooled_size = 0, group_size = 0;
+};
+
+class PSROIPoolingOp {
+ public:
+  explicit PSROIPoolingOp(const PSROIPoolingParam& p) : param_(p) {}
+
+  // psroi_pooling-inl.h:56-80
+  void Forward(const OpContext& ctx, const std::vector<TBlob>& in_data, const std::vector<OpReqType>& req,
+               const std::vector<TBlob>& out_data, const std::vector<TBlob>& aux_args = {}) {
+    RELNET_OP_CHECK(in_data.size() == 2 && out_data.size() == 2, "PSROIPooling: wrong number of blobs");
+    const TShape& d = in_data[psroipool::kData].shape_;
+    const TShape& o = out_data[psroipool::kOut].shape_;
+    RELNET_OP_CHECK(d.size() == 4 && o.size() == 4, "PSROIPooling: 4-D blobs expected");
+    RELNET_OP_CHECK(o[0] == in_data[psroipool::kBox].shape_[0] && out_data[psroipool::kMappingChannel].shape_[0] == o[0],
+                    "output rows must equal the number of rois");
+    const long ds[4] = {d[1] * d[2] * d[3], d[2] * d[3], d[3], 1};
+    const long os[4] = {o[1] * o[2] * o[3], o[2] * o[3], o[3], 1};
+    relnet_call(relnet_psroi_pool_fwd(in_data[psroipool::kData].dptr_, ds, (const float*)in_data[psroipool::kBox].dptr_,
+                                      out_data[psroipool::kOut].dptr_, os, (float*)out_data[psroipool::kMappingChannel].dptr_, (int)o[0],
+                                      (int)d[0], (int)d[1], (int)d[2], (int)d[3], param_.output_dim, param_.pooled_size, param_.group_size,
+                                      param_.spatial_scale, 0, 0, ctx.stream));
+  }
+
+  // psroi_pooling-inl.h:82-122.  The bins are re-derived from the rois (ordered gather, no atomics): kWriteTo needs no zero fill,
+  // kAddTo adds the ordered sum with one addition per word.
+  void Backward(const OpContext& ctx, const std::vector<TBlob>& out_grad, const std::vector<TBlob>& in_data,
+                const std::vector<TBlob>& out_data, const std::vector<OpReqType>& req, const std::vector<TBlob>& in_grad,
+                const std::vector<TBlob>& aux_args = {}) {
+    RELNET_OP_CHECK(in_data.size() == 2 && out_data.size() == 2 && in_grad.size() == 2 && req.size() == 2,
+                    "PSROIPooling.Backward: wrong number of blobs");
+    RELNET_OP_CHECK(out_grad[psroipool::kOut].shape_[0] == in_data[psroipool::kBox].shape_[0] &&
+                    out_data[psroipool::kMappingChannel].shape_[0] == in_data[psroipool::kBox].shape_[0], "rows of out_grad != rois");
+    RELNET_OP_CHECK(req[psroipool::kData] != kWriteInplace && req[psroipool::kBox] != kWriteInplace,
+                    "ROIPooling: Backward doesn't support kWriteInplace.");
+    hipStream_t s = (hipStream_t)ctx.stream;
+    if (req[psroipool::kData] == kAddTo || req[psroipool::kData] == kWriteTo) {
+      const TShape& d = in_grad[psroipool::kData].shape_;
+      const TShape& o = out_grad[psroipool::kOut].shape_;
+      RELNET_OP_CHECK(d.size() == 4 && o.size() == 4, "PSROIPooling.Backward: 4-D blobs expected");
+      const long ds[4] = {d[1] * d[2] * d[3], d[2] * d[3], d[3], 1};
+      const long os[4] = {o[1] * o[2] * o[3], o[2] * o[3], o[3], 1};
+      relnet_call(relnet_psroi_pool_bwd(out_grad[psroipool::kOut].dptr_, os, (const float*)in_data[psroipool::kBox].dptr_,
+                                        (float*)in_grad[psroipool::kData].dptr_, ds, (int)o[0], (int)d[0], (int)d[1], (int)d[2], (int)d[3],
+                                        param_.output_dim, param_.pooled_size, param_.group_size, param_.spatial_scale, 0,
+                                        req[psroipool::kData] == kAddTo ? 1 : 0, 0, s));
+    }
+    if (req[psroipool::kBox] == kWriteTo && in_grad[psroipool::kBox].Size() > 0)                     // grad_roi = 0, :118-120
+      relnet_hipcheck(hipMemsetAsync(in_grad[psroipool::kBox].dptr_, 0, sizeof(float) * in_grad[psroipool::kBox].Size(), s));
+  }
+
+ private:
+  PSROIPoolingParam param_;
+};
+
+class PSROIPoolingProp {                           // psroi_pooling-inl.h:133-231
+ public:
+  explicit PSROIPoolingProp(const PSROIPoolingParam& p) : param_(p) {
+    if (param_.group_size == 0) param_.group_size = param_.pooled_size;                               // Init(), :151-156
+  }
+  std::vector<std::string> ListArguments() const { return {"data", "rois"}; }
+  std::vector<std::string> ListOutputs() const { return {"output", "mapping_channel"}; }
+  int NumOutputs() const { return 2; }
+  int NumVisibleOutputs() const { return 1; }
+  std::string TypeString() const { return "_contrib_PSROIPooling"; }
+  bool InferShape(std::vector<TShape>* in_shape, std::vector<TShape>* out_shape, std::vector<TShape>* aux_shape = nullptr) const {
+    RELNET_OP_CHECK(in_shape->size() == 2, "Input:[data, rois]");
+    const TShape& d = (*in_shape)[psroipool::kData];
+    const TShape& b = (*in_shape)[psroipool::kBox];
+    RELNET_OP_CHECK(d.size() == 4, "data should be a 4D tensor");
+    RELNET_OP_CHECK(b.size() == 2 && b[1] == 5, "bbox should be a 2D tensor of shape [batch, 5]");
+    // not in the reference, whose kernel then reads out of bounds: the channel count the kernel indexes with
+    RELNET_OP_CHECK(d[1] == (long)param_.output_dim * param_.group_size * param_.group_size, "data channels != output_dim * group_size^2");
+    const TShape o = {b[0], (long)param_.output_dim, (long)param_.pooled_size, (long)param_.pooled_size};
+    out_shape->assign(2, o);
+    return true;
+  }
+  bool InferType(std::vector<int>* in_type, std::vector<int>* out_type, std::vector<int>* aux_type = nullptr) const {
+    RELNET_OP_CHECK(in_type->size() == 2, "Input:[data, rois]");
+    const int dtype = (*in_type)[0];
+    RELNET_OP_CHECK(dtype == (*in_type)[1], "data and rois must have one type");
+    RELNET_OP_CHECK(dtype != -1, "Input must have specified type");
+    out_type->assign(2, dtype);
+    return true;
+  }
+  std::vector<int> DeclareBackwardDependency(const std::vector<int>& out_grad, const std::vector<int>& in_data,
+                                             const std::vector<int>& out_data) const {
+    return {out_grad[psroipool::kOut], in_data[psroipool::kBox], out_data[psroipool::kMappingChannel]};
+  }
+  PSROIPoolingOp* CreateOperatorEx() const { return new PSROIPoolingOp(param_); }
+
+ private:
+  PSROIPoolingParam param_;
 };
 
 }  // namespace relnet_op

@@ -53,6 +53,8 @@ _SIGNATURES = {
     'relnet_roi_align_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _vp]),
     'relnet_roi_align_levels_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
     'relnet_roi_align_levels_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
+    'relnet_psroi_pool_fwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 8 + [_f, _i, _i, _vp]),
+    'relnet_psroi_pool_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp] + [_i] * 8 + [_f, _i, _i, _i, _vp]),
     'relnet_roi_pool_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _l, _l, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'relnet_roi_pool_bwd_ex': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'relnet_roi_pool_fpn_bwd_ex': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),

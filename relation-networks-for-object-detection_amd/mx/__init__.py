@@ -61,7 +61,7 @@ contrib = types.ModuleType(__name__ + '.contrib')
 contrib.sym = contrib.symbol = types.ModuleType(__name__ + '.contrib.symbol')
 for _pub, _op in (('DeformableConvolution', '_contrib_DeformableConvolution'),
                   ('DeformablePSROIPooling', '_contrib_DeformablePSROIPooling'), ('Proposal', '_contrib_Proposal'),
-                  ('ROIAlign', '_contrib_ROIAlign')):
+                  ('ROIAlign', '_contrib_ROIAlign'), ('PSROIPooling', '_contrib_PSROIPooling')):
     setattr(contrib.sym, _pub, (lambda o: lambda *a, **k: _R.make(o, a, k))(_op))
 
 # mx.operator: the CustomOp protocol lives in relnet_amd.operator_py (same classes, same registry)

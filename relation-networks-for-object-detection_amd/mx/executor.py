@@ -8,6 +8,7 @@
         Convolution (+ folded BatchNorm + ReLU + shortcut add, fused when the graph spells that chain)
                                    -> relnet_conv2d_nhwc / relnet_stem_conv7 (bf16) ; float32 executor: MIOpen
         FullyConnected, dot, batch_dot -> relnet_gemm_nt ;  ROIPooling -> relnet_roi_pool_fwd
+        contrib.PSROIPooling -> relnet_psroi_pool_fwd
         Pooling(max 3x3/2 'full')  -> relnet_stem_bias_relu_pool ;  Custom(op_type=...) -> operator_py registry
         the ~25-operator `attention_module_multi_head` sub-graph (SYM_REL:85-151 incl. the position
         matrix / embedding, :29-83)  -> geometry + projection + fused attention kernels (relation.py),
@@ -66,7 +67,7 @@ def infer_shapes(sym, known):
 # executor
 # ---------------------------------------------------------------------------------------------------------
 _LOWP_OK = {'Convolution', 'BatchNorm', 'Activation', 'broadcast_add', '_plus', 'elemwise_add', 'FullyConnected', 'ROIPooling', '_contrib_ROIAlign',
-            'Pooling', 'slice_axis', '_contrib_DeformableConvolution', '_contrib_DeformablePSROIPooling', 'Flatten'}
+            'Pooling', 'slice_axis', '_contrib_DeformableConvolution', '_contrib_DeformablePSROIPooling', '_contrib_PSROIPooling', 'Flatten'}
 
 
 def _t(x, device):
@@ -526,4 +527,9 @@ class Executor(object):
             names = OPS[n.op].inputs_for(a)
             kw = dict(zip(names, ins))
             return operator_cxx.contrib.DeformablePSROIPooling(**kw, **{k_: a_get(a, k_) for k_ in a if k_ != 'name'})
+        if n.op == '_contrib_PSROIPooling':
+            from .. import operator_cxx
+            x, rois = ins
+            return operator_cxx.contrib.PSROIPooling(x if x.dtype in (torch.float32, torch.bfloat16) else x.float(), rois,
+                                                     **{k_: a_get(a, k_) for k_ in a if k_ != 'name'})
         raise NotImplementedError("operator %s has no device implementation in this executor" % n.op)

@@ -579,6 +579,8 @@ def _dpsroi_meta(a, x, rois, trans=None):
 
 
 defop('_contrib_DeformablePSROIPooling', _dpsroi_inputs, _dpsroi_meta, heavy=True, hint='deformablepsroipooling')
+# mx.contrib.sym.PSROIPooling(data, rois, spatial_scale, output_dim, pooled_size, group_size) (psroi_pooling-inl.h:33-47): one visible output
+defop('_contrib_PSROIPooling', ['data', 'rois'], _dpsroi_meta, heavy=True, hint='psroipooling')
 
 
 def _proposal_meta(a, cls_prob, bbox_pred, im_info):

@@ -1,5 +1,6 @@
 """Mirror of the reference's C++ operator interface for the DCN configuration
-(relation_rcnn/operator_cxx: `_contrib_DeformableConvolution`, `_contrib_DeformablePSROIPooling`).
+(relation_rcnn/operator_cxx: `_contrib_DeformableConvolution`, `_contrib_DeformablePSROIPooling`) and for the directory's third
+operator, `_contrib_PSROIPooling` (psroi_pooling-inl.h; HIP kernels of csrc/psroi_pool.hip).
 
 The reference registers legacy MXNet operators: a `*Param` struct, an `OperatorProperty`
 (ListArguments / ListOutputs / InferShape) and an `Operator` with `Forward(ctx, in_data, req,
@@ -277,8 +278,122 @@ class DeformablePSROIPoolingOp(object):
             _assign(in_grad[2], req[2], gtrans)
 
 
+class PSROIPoolingParam(object):
+    """psroi_pooling-inl.h:33-47 (group_size defaults to 0 = pooled_size, resolved by the Prop's Init)."""
+
+    def __init__(self, spatial_scale, output_dim, pooled_size, group_size=0):
+        self.spatial_scale = float(spatial_scale)
+        if not 0.0 <= self.spatial_scale <= 1.0:
+            raise ValueError("spatial_scale out of range [0, 1]")
+        self.output_dim, self.pooled_size, self.group_size = int(output_dim), int(pooled_size), int(group_size)
+
+
+class PSROIPoolingProp(object):
+    """OperatorProperty of `_contrib_PSROIPooling` (psroi_pooling-inl.h:133-231)."""
+
+    def __init__(self, **kwargs):
+        self.param_ = PSROIPoolingParam(**kwargs)
+        if self.param_.group_size == 0:                                   # Init(), :151-156
+            self.param_.group_size = self.param_.pooled_size
+
+    def ListArguments(self):
+        return ['data', 'rois']
+
+    def ListOutputs(self):
+        return ['output', 'mapping_channel']
+
+    def NumOutputs(self):
+        return 2
+
+    def NumVisibleOutputs(self):
+        return 1
+
+    def InferShape(self, in_shape):
+        """:162-185, plus the channel count the kernel indexes with: C == output_dim * group_size^2 (the reference reads out of bounds)."""
+        p = self.param_
+        if len(in_shape) != 2:
+            raise ValueError("Input:[data, rois]")
+        dshape, bshape = tuple(in_shape[0]), tuple(in_shape[1])
+        if len(dshape) != 4:
+            raise ValueError("data should be a 4D tensor")
+        if len(bshape) != 2 or bshape[1] != 5:
+            raise ValueError("bbox should be a 2D tensor of shape [batch, 5]")
+        if dshape[1] != p.output_dim * p.group_size * p.group_size:
+            raise ValueError("data has %d channels, output_dim * group_size^2 = %d" % (dshape[1], p.output_dim * p.group_size ** 2))
+        out = (bshape[0], p.output_dim, p.pooled_size, p.pooled_size)
+        return list(in_shape), [out, out]
+
+    def InferType(self, in_type):
+        """:187-199: both inputs one specified dtype; both outputs take it."""
+        if len(in_type) != 2 or in_type[0] is None or in_type[0] != in_type[1]:
+            raise ValueError("Input must have specified type, the same for data and rois")
+        return list(in_type), [in_type[0], in_type[0]]
+
+    def TypeString(self):
+        return '_contrib_PSROIPooling'
+
+    def DeclareBackwardDependency(self, out_grad, in_data, out_data):
+        return [out_grad[0], in_data[1], out_data[1]]                    # :212-217: kOut grad, kBox, kMappingChannel
+
+    def CreateOperatorEx(self, ctx=None, in_shape=None, in_type=None):
+        return PSROIPoolingOp(self.param_)
+
+
+class PSROIPoolingOp(object):
+    """PSROIPoolingOp::Forward / Backward (psroi_pooling-inl.h:56-122) over relnet_psroi_pool_fwd / relnet_psroi_pool_bwd."""
+
+    def __init__(self, param):
+        self.param_ = param
+
+    def Forward(self, ctx, in_data, req, out_data, aux_args=None):
+        p = self.param_
+        if len(in_data) != 2 or len(out_data) != 2:
+            raise ValueError("PSROIPooling: wrong number of inputs / outputs")
+        data, rois = in_data
+        if out_data[0].shape[0] != rois.shape[0] or out_data[1].shape[0] != rois.shape[0]:
+            raise ValueError("PSROIPooling: output rows must equal the number of rois")
+        for t in (data, rois, out_data[0], out_data[1]):
+            if not t.is_contiguous():
+                raise ValueError("PSROIPooling: tensors must be contiguous (psroi_pooling-inl.h:73-76)")
+        out, mapping = ops.psroi_pool(data, rois.float(), p.spatial_scale, p.output_dim, p.pooled_size, p.group_size, want_mapping=True)
+        out_data[0].copy_(out)
+        out_data[1].copy_(mapping)
+
+    def Backward(self, ctx, out_grad, in_data, out_data, req, in_grad, aux_args=None):
+        """:82-122: in_grad = [d data, d rois]; req[kData] 'write' overwrites, 'add' accumulates, 'null' leaves it alone; the rois
+        gradient is zeroed on 'write' (:118-120); kWriteInplace is rejected like there.  The bins are re-derived from the rois (the
+        ordered gather of relnet_psroi_pool_bwd), so mapping_channel is checked for its rows only."""
+        p = self.param_
+        if len(in_data) != 2 or len(out_data) != 2 or len(in_grad) != 2 or len(req) != 2:
+            raise ValueError("PSROIPooling.Backward: wrong number of inputs / outputs")
+        if req[0] == kWriteInplace or req[1] == kWriteInplace:
+            raise ValueError("ROIPooling: Backward doesn't support kWriteInplace.")
+        rois = in_data[1]
+        if out_grad[0].shape[0] != rois.shape[0] or out_data[1].shape[0] != rois.shape[0]:
+            raise ValueError("PSROIPooling.Backward: rows of out_grad / mapping_channel must equal the number of rois")
+        if req[0] in (kWriteTo, kAddTo):
+            gdata = in_grad[0]
+            g = out_grad[0] if out_grad[0].dtype in (torch.float32, torch.bfloat16) else out_grad[0].float()
+            direct = gdata.dtype == torch.float32
+            got = ops.psroi_pool_bwd(g, rois.float().contiguous(), tuple(gdata.shape), p.spatial_scale, p.output_dim, p.pooled_size,
+                                     p.group_size, accumulate_into=gdata if direct and req[0] == kAddTo else None)
+            if not (direct and req[0] == kAddTo):
+                _assign(gdata, req[0], got)
+        elif req[0] != kNullOp:
+            raise ValueError('unknown OpReqType %r' % (req[0],))
+        if req[1] == kWriteTo:
+            in_grad[1].zero_()
+
+
 class contrib(object):
-    """Eager counterparts of `mx.contrib.sym.DeformableConvolution` / `DeformablePSROIPooling`."""
+    """Eager counterparts of `mx.contrib.sym.DeformableConvolution` / `DeformablePSROIPooling` / `PSROIPooling`."""
+
+    @staticmethod
+    def PSROIPooling(data, rois, name=None, **attrs):
+        prop = PSROIPoolingProp(**attrs)
+        prop.InferShape([tuple(data.shape), tuple(rois.shape)])
+        p = prop.param_
+        return ops.psroi_pool(data, rois.float().contiguous(), p.spatial_scale, p.output_dim, p.pooled_size, p.group_size)      # one visible output
 
     @staticmethod
     def DeformableConvolution(data, offset, weight, bias=None, name=None, **attrs):

@@ -433,6 +433,50 @@ def roi_align_bwd(grad_out, rois, in_shape, spatial_scale=0.0625, sampling_ratio
     return gin
 
 
+def _psroi_group(group_size, pooled_size):
+    return int(pooled_size) if int(group_size) == 0 else int(group_size)          # PSROIPoolingProp::Init, psroi_pooling-inl.h:153-155
+
+
+def psroi_pool(data, rois, spatial_scale, output_dim, pooled_size, group_size=0, channels_last_out=False, want_mapping=False,
+               batch_index_base=0):
+    """PSROIPooling (relnet_psroi_pool_fwd; mx.contrib.sym.PSROIPooling(data, rois, spatial_scale, output_dim, pooled_size, group_size),
+    psroi_pooling.cu:32-101).  data: logical [B, output_dim * g * g, H, W] of any strides, fp32 / bf16 (g = group_size, 0 = pooled_size);
+    rois [R,5] fp32.  Output logical [R, output_dim, P, P] in data's dtype (memory (R,P,P,output_dim) when channels_last_out);
+    want_mapping adds the operator's second output, the fp32 input channel of every bin, with the output's strides."""
+    _chk(data, rois)
+    assert rois.dtype == torch.float32 and rois.is_contiguous()
+    B, Cc, H, W = data.shape
+    R, P, G = rois.shape[0], int(pooled_size), _psroi_group(group_size, pooled_size)
+    out = _pooled_out(R, int(output_dim), P, P, channels_last_out, data.device, data.dtype)
+    mapping = torch.empty_strided(out.shape, out.stride(), device=data.device, dtype=torch.float32) if want_mapping else None
+    _lib.call('relnet_psroi_pool_fwd', data.data_ptr(), _strides4(data), rois.data_ptr(), out.data_ptr(), _strides4(out), _ptr(mapping),
+              R, B, Cc, H, W, int(output_dim), P, G, float(spatial_scale), batch_index_base, _dt(data), _stream())
+    return (out, mapping) if want_mapping else out
+
+
+def psroi_pool_bwd(grad_out, rois, in_shape, spatial_scale, output_dim, pooled_size, group_size=0, channels_last=False,
+                   accumulate_into=None, batch_index_base=0):
+    """Adjoint of psroi_pool (relnet_psroi_pool_bwd, psroi_pooling.cu:132-194 as an ordered gather): grad_out logical
+    [R, output_dim, P, P] of any strides, fp32 / bf16 -> fp32 gradient of the feature map, logical in_shape = (B,C,H,W); memory NCHW, or
+    NHWC with channels_last.  Every word is written with the fp32 sum of its contributions in ascending (roi, ph, pw) order: no atomics,
+    no zero fill, the same bits on every call.  accumulate_into: an fp32 tensor of in_shape (any strides) that receives `+=` of that sum
+    instead (kAddTo) and is returned."""
+    _chk(grad_out, rois, accumulate_into)
+    assert rois.dtype == torch.float32 and rois.is_contiguous()
+    B, Cc, H, W = in_shape
+    R, P, G = grad_out.shape[0], int(pooled_size), _psroi_group(group_size, pooled_size)
+    assert tuple(grad_out.shape) == (rois.shape[0], int(output_dim), P, P)
+    if accumulate_into is not None:
+        assert accumulate_into.dtype == torch.float32 and tuple(accumulate_into.shape) == tuple(in_shape)
+        gin = accumulate_into
+    else:
+        gin, = _map_grads([in_shape], channels_last, grad_out.device, zero=False)
+    _lib.call('relnet_psroi_pool_bwd', grad_out.data_ptr(), _strides4(grad_out), rois.data_ptr(), gin.data_ptr(), _strides4(gin), R, B, Cc,
+              H, W, int(output_dim), P, G, float(spatial_scale), batch_index_base, int(accumulate_into is not None), _dt(grad_out),
+              _stream())
+    return gin
+
+
 # ---------------------------------------------------------------------------------------
 # detection post-processing
 # ---------------------------------------------------------------------------------------
