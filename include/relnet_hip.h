@@ -188,6 +188,23 @@ int relnet_stem_conv7(const void* packed, const void* w256, const float* bias, i
  * 30-36, fused into one pass over the NHWC stem output: out = relu(maxpool_ceil(in) + bias).        */
 int relnet_stem_bias_relu_pool(const void* in, const float* bias, void* out, int B, int H, int W, int C,
                                int ksize, int stride, void* stream);
+/* ---- the stem's backward (csrc/stem_bwd.hip), for a step whose network.FIXED_PARAMS leaves conv1 trainable.
+ * relnet_stem_pool_bwd: adjoint of relnet_stem_bias_relu_pool (ksize 3, stride 2; bn_conv1 -> conv1_relu -> pool1,
+ * resnet_v1_101_rcnn_base.py:30-36).  conv [B,H,W,C] is the map before bias, out / d_out [B,Ho,Wo,C]; dtype 0 fp32 (C % 4 == 0),
+ * 1 bf16 (C % 8 == 0); d_conv [B,H,W,C] in that dtype.  A window hands d_out * (out > 0) to its FIRST maximum in row-major window
+ * order (MXNet's unpool rule and torch's; a restatement: the reference has no pooling source).  A gather: a conv pixel sums the at
+ * most 2 x 2 windows covering it in ascending (ph, pw), in fp32 from 0, rounded once -- no float atomics, no zero fill.        */
+int relnet_stem_pool_bwd(const void* conv, const void* out, const void* d_out, void* d_conv, int B, int H, int W, int C, int dtype,
+                         void* stream);
+/* relnet_stem_wgrad: weight gradient of conv1 7x7/2 pad 3 (resnet_v1_101_rcnn_base.py:30-31): dw[64][147] ((ty, tx, c) order, rows
+ * of dw_ld floats) += row_scale^2 (null: 1) * sum over the B*Hc*Wc pixels of d_conv[p, :]^T patch[p, :].  packed [B,Hp,Wp,4] bf16
+ * from relnet_stem_pack_input (pad 3), d_conv [B,Hc,Wc,64] bf16.  fp32 accumulation on MFMA in the k order of ops.pack_stem_weight;
+ * the pixels are cut into ceil(B*Hc*Wc / 4096) chunks (a function of the shape only), each chunk's sum goes to the workspace
+ * (relnet_stem_wgrad_workspace_bytes(B, Hc, Wc) bytes, no initialisation needed) and a second kernel adds the partials in ascending
+ * chunk order: no float atomics, the same bits on every run.                                                                    */
+long relnet_stem_wgrad_workspace_bytes(int B, int Hc, int Wc);
+int relnet_stem_wgrad(const void* packed, const void* d_conv, float* dw, long dw_ld, const float* row_scale, void* workspace,
+                      long workspace_bytes, int B, int Hp, int Wp, int Hc, int Wc, void* stream);
 /* conv1 7x7/2 (pad 3) + folded-BN bias + ReLU + pool1 3x3/2 (pooling_convention='full') in ONE kernel, raw NCHW image ->
  * pooled NHWC bf16 map (resnet_v1_101_rcnn_base.py:30-36): bit-identical to relnet_stem_pack_input + relnet_stem_conv7 +
  * relnet_stem_bias_relu_pool without the conv map's HBM round trip.  data [B,3,H,W] (in_dtype 0 fp32 / 1 bf16),

@@ -332,6 +332,17 @@ class Backbone(object):
             x, y_next = self._unit_hip(x, unit, y_next)
         return x
 
+    def forward_stem(self, data, im_info=None):
+        """conv1 + bn_conv1 + ReLU + pool1 only (a training step whose res2 is trainable above a fixed conv1): the fused stem, or its
+        float32 twin -> pooled NHWC map."""
+        if self.impl == 'hip32':
+            data = self._float_image(data, im_info, torch.float32)
+            B, Cin, H, W = data.shape
+            x = torch.zeros((B, H, W, 16), device=data.device, dtype=torch.float32)
+            x[..., :Cin] = data.permute(0, 2, 3, 1)
+            return ops.maxpool_nhwc_f32(self._c32(x, 'conv1', stride=2, pad=3, relu=True), 3, 2)
+        return ops.stem_fused(data, self.w_stem, self.b32['conv1'], im_info, self.pixel_means)
+
     def _forward_hip(self, data, rpn_hook=None, im_info=None):
         if self.stem == 'hip':
             # conv1 7x7/2 + bias + ReLU + pool1 in ONE kernel, raw NCHW (or uint8 HWC) image -> pooled NHWC map (no conv map in HBM)
@@ -581,6 +592,9 @@ RPN_WGRAD_WORKGROUPS = 64
 
 #: what the training forward keeps of one unit for its adjoint (off: (offset map, sampled column matrix) of a deformable unit | None)
 SavedUnit = namedtuple('SavedUnit', 'stage nm stride dil proj x y1 y2 out off')
+#: ... and of a trainable stem: image = what conv1's weight gradient reads (the packed NHWC4 bf16 image; the float NCHW image for the float32
+#: trunk), conv = the conv1 map before bias, out = relu(pool1(conv) + bias)
+SavedStem = namedtuple('SavedStem', 'image conv out')
 
 
 class TrunkTrain(object):
@@ -622,12 +636,18 @@ class TrunkTrain(object):
 
     # ---- res3 .. res5 ----------------------------------------------------------------------------------------
     def forward(self, data, at_conv4=None, im_info=None):
-        """Frozen stem + res2, then res3..res5 keeping every ReLU output.  Returns (conv5, conv4, saved units, stage ends).
+        """Frozen stem + res2 (or, where network.FIXED_PARAMS leaves them trainable, res2 / conv1 on the trainer's weights like the rest), then
+        res3..res5 keeping every ReLU output.  Returns (conv5, conv4, saved units, stage ends).
         at_conv4(conv4): called once conv4 exists, before res5 is queued (the RPN branch forks there).  data: float NCHW or uint8
         [B,H,W,3] BGR HWC (Backbone.forward; im_info gives each image's extent)."""
         t = self.t
-        x = t._frozen_backbone.forward_res2(data, im_info)      # (float32 NHWC for the float32 trunk: Backbone impl 'hip32')
         saved = []
+        if t.stem_trainable:       # conv1 .. res5 on the trainer's weights; saved[0] is the stem's SavedStem
+            x = self._stem_forward(data, im_info, saved)
+        elif t.res2_trainable:     # fixed conv1 on the fused stem, res2 .. res5 on the trainer's weights
+            x = t._frozen_backbone.forward_stem(data, im_info)
+        else:
+            x = t._frozen_backbone.forward_res2(data, im_info)      # (float32 NHWC for the float32 trunk: Backbone impl 'hip32')
         y_pre = None               # reduce output of the coming unit when the previous unit's chain kernel already produced it
 
         def deform(y1, nb):        # 72-channel offset conv -> DeformableConvolution(num_deformable_group=4) + BN + ReLU
@@ -654,13 +674,60 @@ class TrunkTrain(object):
             y1, y2, off = kept
             saved.append(SavedUnit(unit[0], nm, unit[5], unit[6], unit[7], x, y1, y2, out, off))
             return out
-        conv5, conv4, ends = walk_units([u for u in t.units if u[0] > 2], x, unit_fn, at_conv4)       # (res2 ran inside forward_res2)
+        # (fixed res2 ran inside forward_res2; a trainable one takes the same unit path as res3 .. res5, on the per-layer convolutions:
+        # its block boundaries have no fragment copies in _fragpack, and the quarter form is not used)
+        conv5, conv4, ends = walk_units([u for u in t.units if u[0] > 2 or t.res2_trainable], x, unit_fn, at_conv4)
         ends[5] = conv5
         return conv5, conv4, saved, ends
+
+    def _stem_forward(self, data, im_info, saved):
+        """Trainable stem: the three-launch form (pack, 7x7 / 2 convolution WITHOUT bias and ReLU, bias + ReLU + pool1) on the trainer's conv1,
+        keeping what its adjoint reads (appended to `saved` as a SavedStem).  -> pooled NHWC map."""
+        t = self.t
+        fb = t._frozen_backbone
+        img = fb._float_image(data, im_info, torch.float32)
+        w = t.w('conv1').view(64, 7, 7, 3)                    # folded weights, (ty, tx, c) columns
+        bias = t.conv_bias['conv1']
+        if t.trunk_fp32:           # exact-fp32 convolution on the image zero-padded to 16 channels, relnet_maxpool_nhwc_f32, bias + ReLU
+            B, Cin, H, W = img.shape
+            x = torch.zeros((B, H, W, 16), device=img.device, dtype=torch.float32)
+            x[..., :Cin] = img.permute(0, 2, 3, 1)
+            wz = torch.zeros((64, 7, 7, 16), device=img.device, dtype=torch.float32)
+            wz[..., :3] = w
+            conv = ops.conv2d_nhwc_f32(x, wz.view(64, -1), None, ksize=7, stride=2, pad=3)
+            out = torch.relu_(ops.maxpool_nhwc_f32(conv, 3, 2) + bias)
+            saved.append(SavedStem(img, conv, out))
+            return out
+        w256 = torch.zeros((64, 8, 8, 4), device=img.device, dtype=torch.bfloat16)      # ops.pack_stem_weight's layout, from the working copy
+        w256[:, :7, :7, :3] = w
+        conv, packed = ops.stem_conv7(img, w256.view(64, 256), None, relu=False, want_packed=True)
+        out = ops.stem_bias_relu_pool(conv, bias)
+        saved.append(SavedStem(packed, conv, out))
+        return out
+
+    def _stem_backward(self, stem, d_out):
+        """d_out = gradient of the pooled map -> conv1's weight gradient (conv1 reads the image: no data gradient)."""
+        t = self.t
+        d_conv = ops.stem_pool_bwd(stem.conv, stem.out, d_out.contiguous())
+        g, scale, _ = t._wg('conv1', t.bn_scale['conv1'])
+        if not t.trunk_fp32:
+            ops.stem_wgrad(stem.image, d_conv, g, scale)
+            return
+        # float32 trunk (parity tests): conv1's column matrix by unfold, the product on the float32 GEMM
+        B = stem.image.shape[0]
+        col = F.unfold(stem.image, 7, padding=3, stride=2)                                   # [B, (c, ty, tx), pixels]
+        col = col.view(B, 3, 49, -1).permute(0, 3, 2, 1).reshape(-1, 147)                    # [pixels, (ty, tx, c)]
+        colp = torch.zeros((col.shape[0], 160), device=col.device, dtype=torch.float32)
+        colp[:, :147] = col
+        dw = T.wgrad(d_conv.reshape(-1, 64), colp)
+        g.add_(dw[:, :147] * (scale * scale).view(-1, 1))
 
     def backward(self, saved, d_x, inject):
         """res5 -> res3 backward.  d_x = gradient of the last unit's output; inject[unit] = extra gradient of that unit's output."""
         t = self.t
+        stem = None
+        if isinstance(saved[0], SavedStem):       # trainable conv1: its adjoint follows res2a's
+            stem, saved = saved[0], saved[1:]
         B = saved[0].x.shape[0]
         bt = torch.bfloat16
         # trunk: res5 -> res3.  Gradient buckets are announced as they complete (heads first; with DCN the res5 offset
@@ -709,7 +776,9 @@ class TrunkTrain(object):
                                          relu_mask=y1)
             prev_nm = order[pos + 1].nm if pos + 1 < len(order) else None
             if s.proj:
-                first = s.stage == 3          # res3a: its input comes from the frozen res2 -> no data gradient
+                # this unit's input has no trainable layer below it -> no data gradient: res3a above a fixed res2 (every shipped list), res2a
+                # above a fixed conv1
+                first = (s.stage == 3 and not t.res2_trainable) or (s.stage == 2 and not t.stem_trainable)
                 # both branches read the same (sampled) input: their data gradients are summed in the second GEMM's epilogue -- at the SAMPLED
                 # resolution for a stride-2 unit, then scattered to the input's resolution once, with the previous unit's ReLU mask in the same
                 # pass when that output has no other consumer (was: 2 zero fills + 2 strided copies + a full-resolution add + relu_bwd)
@@ -739,6 +808,8 @@ class TrunkTrain(object):
                 d_x, dw = T.conv1x1_bwd(x_in, t.w(na), g_y1, dx_add=g_out, w_t=t.wt(na), keep_splits=True, wgrad_to=t._wg(na, t.bn_scale[na]),
                                         out_mask=x_in if can_mask else None)
                 masked = can_mask
+        if stem is not None:          # d_x: gradient of the pooled map (res2a's two branches summed, unmasked: pool_bwd applies out > 0)
+            self._stem_backward(stem, d_x)
         t._bucket_ready(prev_bucket)
 
     # ---- FPN neck --------------------------------------------------------------------------------------------

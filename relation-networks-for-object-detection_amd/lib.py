@@ -190,6 +190,10 @@ _SIGNATURES = {
     'relnet_geometry_bias_bwd_ordered': (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp]),
     'relnet_lnms_take_bwd_ordered': (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'relnet_wgrad_grouped_ex': (C.c_int, [_vp, _i, _vp, _i, _i, _vp]),
+    # the stem's backward (network.FIXED_PARAMS without conv1): ordered by construction
+    'relnet_stem_pool_bwd': (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'relnet_stem_wgrad_workspace_bytes': (C.c_long, [_i, _i, _i]),
+    'relnet_stem_wgrad': (C.c_int, [_vp, _vp, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -1267,8 +1267,9 @@ def pack_stem_weight(w_oihw, dtype=torch.bfloat16, device='cuda'):
     return w.reshape(co, 256).to(device=device, dtype=dtype).contiguous()
 
 
-def stem_conv7(data, w256, bias, relu=True):
-    """data [B,3,H,W] fp32/bf16 NCHW contiguous -> relu(conv 7x7 / 2, pad 3) as NHWC bf16 [B,Ho,Wo,Cout]."""
+def stem_conv7(data, w256, bias, relu=True, want_packed=False):
+    """data [B,3,H,W] fp32/bf16 NCHW contiguous -> relu(conv 7x7 / 2, pad 3) as NHWC bf16 [B,Ho,Wo,Cout] (bias None: no bias).
+    want_packed: -> (out, the zero-padded NHWC4 bf16 image the convolution read: stem_wgrad's operand)."""
     _chk(data, w256, bias)
     data = data.contiguous()
     B, Cin, H, W = data.shape
@@ -1282,7 +1283,50 @@ def stem_conv7(data, w256, bias, relu=True):
     out = torch.empty((B, Ho, Wo, Cout), device=data.device, dtype=torch.bfloat16)
     _lib.call('relnet_stem_conv7', packed.data_ptr(), w256.data_ptr(), _ptr(bias), int(relu), out.data_ptr(), Cout,
               B, Hp, Wp, Ho, Wo, Cout, _dt(out), _stream())
-    return out
+    return (out, packed) if want_packed else out
+
+
+def stem_pool_bwd(conv, out, d_out):
+    """Adjoint of `stem_bias_relu_pool` (3x3 / 2, ceil mode; float32: of maxpool_nhwc_f32 + bias + ReLU): conv [B,H,W,C] the map before bias,
+    out = relu(maxpool_ceil(conv) + bias) and d_out [B,Ho,Wo,C], all bf16 or all float32 -> d_conv [B,H,W,C] in that dtype.  A window hands
+    d_out * (out > 0) to its first maximum in row-major order; each conv pixel gathers its at most four windows in ascending (ph, pw)
+    (relnet_stem_pool_bwd: no float atomics)."""
+    _chk(conv, out, d_out)
+    assert conv.dtype in (torch.bfloat16, torch.float32) and out.dtype == conv.dtype and d_out.dtype == conv.dtype
+    assert conv.is_contiguous() and out.is_contiguous() and d_out.is_contiguous() and out.shape == d_out.shape
+    B, H, W, Cc = conv.shape
+    Ho, Wo = _pool_ceil_hw(H, W)
+    assert tuple(out.shape) == (B, Ho, Wo, Cc), "out is %s, a [%d,%d,%d,%d] conv map pools to %s" % (tuple(out.shape), B, H, W, Cc, (B, Ho, Wo, Cc))
+    d_conv = torch.empty_like(conv)
+    _lib.call('relnet_stem_pool_bwd', conv.data_ptr(), out.data_ptr(), d_out.data_ptr(), d_conv.data_ptr(), B, H, W, Cc, _dt(conv), _stream())
+    return d_conv
+
+
+def _pool_ceil_hw(H, W, ksize=3, stride=2):
+    Ho, Wo = -(-(H - ksize) // stride) + 1, -(-(W - ksize) // stride) + 1
+    if (Ho - 1) * stride >= H:
+        Ho -= 1
+    if (Wo - 1) * stride >= W:
+        Wo -= 1
+    return Ho, Wo
+
+
+def stem_wgrad(packed, d_conv, dw, row_scale=None):
+    """dw [64, 147] fp32 ((ty, tx, c) columns, a view with unit column stride) += row_scale^2 * conv1's weight gradient: packed [B,Hp,Wp,4] bf16
+    (stem_conv7(want_packed=True)), d_conv [B,Hc,Wc,64] bf16.  relnet_stem_wgrad: MFMA partial sums per chunk of 4096 pixels into a workspace,
+    added in ascending chunk order -- no float atomics, the same bits on every run.  Returns the workspace (alive until the launch has run)."""
+    _chk(packed, d_conv, dw, row_scale)
+    assert packed.dtype == torch.bfloat16 and d_conv.dtype == torch.bfloat16 and packed.is_contiguous() and d_conv.is_contiguous()
+    assert dw.dtype == torch.float32 and tuple(dw.shape) == (64, 147) and dw.stride(1) == 1
+    assert row_scale is None or (row_scale.dtype == torch.float32 and row_scale.numel() == 64 and row_scale.is_contiguous())
+    B, Hp, Wp, four = packed.shape
+    Bd, Hc, Wc, Cc = d_conv.shape
+    assert four == 4 and Bd == B and Cc == 64
+    nbytes = int(_lib.load().relnet_stem_wgrad_workspace_bytes(B, Hc, Wc))
+    ws = torch.empty(nbytes // 4, device=d_conv.device, dtype=torch.float32)
+    _lib.call('relnet_stem_wgrad', packed.data_ptr(), d_conv.data_ptr(), dw.data_ptr(), dw.stride(0), _ptr(row_scale), ws.data_ptr(), nbytes,
+              B, Hp, Wp, Hc, Wc, _stream())
+    return ws
 
 
 # ---------------------------------------------------------------------------------------

@@ -7,7 +7,7 @@ ROIPooling -> fc_new_1 -> relation_1 -> fc_new_2 -> relation_2 (keys = the first
 -> BoxAnnotatorOHEM (128) -> SoftmaxOutput / smooth_l1 losses; then the adjoint of all of it, ONE summed all-reduce
 of the trainable gradients (core/module.py + kvstore 'device' in the reference, rescale_grad = 1.0) and
 mx.optimizer.SGD (momentum 0.9, wd 5e-4; train_end2end.py:163-168).  Frozen, as cfgs/*.yaml:23-29: conv1, res2 and
-every BatchNorm gamma / beta.  With cfg.learn_nms the learn-NMS head's train branch (symbols/..._learn_nms.py:424-551:
+every BatchNorm gamma / beta (a cfg.fixed_params list without res2 / conv1 trains them too: check_fixed_params).  With cfg.learn_nms the learn-NMS head's train branch (symbols/..._learn_nms.py:424-551:
 per-class sort, rank + appearance embedding, class-batched relation module, sigmoid x score, pos / neg log losses
 against nms_multi_target) is trained jointly = BASELINE configs[2].
 
@@ -52,7 +52,8 @@ class TrainConfig(Config):
     bbox_stds = (0.1, 0.1, 0.2, 0.2)
     relation = True               # two relation modules in the 2FC head (False: the plain head of resnet_v1_101_rcnn_learn_nms_1024_...)
     enable_ohem = True            # TRAIN.ENABLE_OHEM (False: SoftmaxOutput over all rois, bbox loss scaled by 1 / 300)
-    fixed_params = None           # network.FIXED_PARAMS of the experiment file (None: dist.FIXED_PARAMS, the end2end yamls' list)
+    fixed_params = None           # network.FIXED_PARAMS of the experiment file (None: dist.FIXED_PARAMS, the end2end yamls' list).  A list without
+                                  # 'res2' (and 'conv1') trains them too, e.g. ['gamma', 'beta'], config/config.py:40 (check_fixed_params)
     deterministic = False         # True: every float accumulation of the step whose order the hardware would decide (float atomics: ROI pooling
                                   # backward, bias-gradient column sums, loss scalars, the geometry backward, the learn-NMS take adjoint, the
                                   # stream-K weight-gradient flush) runs its ordered form -- two steps from the same state give the same bits
@@ -108,6 +109,36 @@ def check_deterministic(cfg):
         raise ValueError("deterministic training does not cover cfg.dcn: deformable_psroi_pool_bwd and deformable_col2im accumulate with float atomics")
     if getattr(cfg, 'roi_align', False):
         raise ValueError("deterministic training does not cover cfg.roi_align: roi_align_bwd accumulates with float atomics")
+
+
+def check_fixed_params(cfg):
+    """cfg.fixed_params (network.FIXED_PARAMS; a parameter is fixed when ANY pattern is a substring of its name, core/module.py:753-764) as
+    far as it concerns the bottom of the trunk.  -> (conv1 is trainable, res2 is trainable).  Built: the shipped lists (both fixed), res2
+    trainable above a fixed conv1, both trainable.  Refused by name: a trainable conv1 under a fixed res2, a list that leaves BatchNorm
+    gamma / beta trainable (the affine terms and the statistics stay fixed, folded into the convolutions), and a trainable res2 in the FPN
+    graphs."""
+    fixed = getattr(cfg, 'fixed_params', None)
+    if fixed is None:
+        return False, False
+    fixed = tuple(fixed)
+    for term in ('gamma', 'beta'):
+        loose = [n for n in ('bn_conv1_' + term, 'bn2a_branch1_' + term, 'bn4b7_branch2b_' + term, 'bn5c_branch2c_' + term) if D.is_trainable(n, fixed)]
+        if loose:
+            raise ValueError("fixed_params %s leaves BatchNorm %s trainable (%s): the BatchNorm affine terms and statistics are folded into the "
+                             "convolutions and stay fixed -- 'gamma' and 'beta' are missing from the list" % (list(fixed), term, loose[0]))
+    conv1 = D.is_trainable('conv1_weight', fixed)
+    res2 = [D.is_trainable(conv + '_weight', fixed) for conv, _, _, _, _ in conv_bn_names() if conv.startswith('res2')]
+    if any(res2) and not all(res2):
+        raise ValueError("fixed_params %s fixes some res2 convolutions and not others: res2 is trainable or fixed as a whole -- the pattern 'res2' "
+                         "is missing" % (list(fixed),))
+    res2 = all(res2)
+    if conv1 and not res2:
+        raise ValueError("fixed_params %s leaves conv1 trainable under a fixed res2: conv1's gradient needs the data gradient through res2, which a "
+                         "fixed res2 (run on the inference kernels) does not produce -- 'conv1' is missing from the list, or 'res2' must leave it" % (list(fixed),))
+    if res2 and getattr(cfg, 'fpn', False):
+        raise ValueError("fixed_params %s leaves res2 trainable in an FPN graph: the lateral gradient of fpn_ft4_1x1 into res2c is missing "
+                         "(FPNTrainer treats res2c as fixed) -- 'res2' and 'conv1' must stay in the list" % (list(fixed),))
+    return conv1, res2
 
 
 def check_batch_rois(cfg):
@@ -219,6 +250,8 @@ class Trainer(object):
         self.cfg = cfg or TrainConfig()
         check_deterministic(self.cfg)       # (its user-facing messages come before the pooler's assertions)
         c = self.cfg
+        # conv1 / res2 join the trainable trunk when network.FIXED_PARAMS leaves them out (both False for every shipped list)
+        self.stem_trainable, self.res2_trainable = check_fixed_params(c)
         self.deterministic = bool(getattr(c, 'deterministic', False))       # read ONCE: every site below routes on this attribute
         self.fpn = bool(getattr(c, 'fpn', False))
         self.pool = RoiPooling(c, self.scales if self.fpn else (1.0 / c.feat_stride,), deterministic=self.deterministic)
@@ -240,17 +273,20 @@ class Trainer(object):
         self.units = unit_names(self.fpn)
         # the tensors this step never changes (frozen by name, cfgs/*.yaml:23-29, and the BatchNorm running statistics):
         # kept on the host under the reference's names so that a checkpoint holds the complete arg / aux dictionaries
+        # (a list that leaves res2 / conv1 trainable is followed here too: their initial tensors are not kept, the checkpoint holds the updated ones)
+        src_fixed = tuple(c.fixed_params) if self.res2_trainable else D.FIXED_PARAMS
         self._fixed_src = {k: torch.as_tensor(v).detach().to('cpu', torch.float32).clone() for k, v in params.items()
-                           if ('moving_' in k) or not D.is_trainable(k)}
-        # ---- frozen part: conv1 + res2 never change; they run on the inference kernels (fused stem, halo 3x3, chain kernels) of a
-        # Backbone built from the same parameters with folded BN
+                           if ('moving_' in k) or not D.is_trainable(k, src_fixed)}
+        # ---- frozen part: conv1 + res2 never change under the shipped lists; they run on the inference kernels (fused stem, halo 3x3, chain
+        # kernels) of a Backbone built from the same parameters with folded BN.  (With a trainable res2 it still runs a fixed conv1's fused
+        # stem and the uint8 image transform.)
         from .backbone import Backbone
         self._frozen_backbone = Backbone(params, dtype=torch.float32 if self.trunk_fp32 else torch.bfloat16, device=dev, fpn=self.fpn,
                                          frozen_only=True, pixel_means=c.pixel_means)
         weights, biases = [], []
         self.bn_scale, self.conv_bias, self.ksize = {}, {}, {'rpn_conv_3x3': 3, 'rpn_out': 1, 'conv_new_1': 1}
         for conv, bn, oc, ic, k in conv_bn_names():
-            if conv == 'conv1' or conv.startswith('res2'):
+            if (conv == 'conv1' and not self.stem_trainable) or (conv.startswith('res2') and not self.res2_trainable):
                 continue
             w, b = fold_bn(params[conv + '_weight'], params[bn + '_gamma'], params[bn + '_beta'],
                            params[bn + '_moving_mean'], params[bn + '_moving_var'])
@@ -362,8 +398,9 @@ class Trainer(object):
             if name == 'nms_logit':                          # [T,128] -> [128, 64] (T real columns): data-gradient operand of the learn-NMS logit layer
                 self._relayout.add(name, self.w(name), taps=1, pad_co=64)
                 continue
-            if name.startswith(('pair_pos_fc1', 'nms_')) or name.endswith('_offset') or self._trunk32(name):
-                continue                                    # consumed in other layouts (relation_bwd kernels, padded DCN offset convs; float32 trunk)
+            if name.startswith(('pair_pos_fc1', 'nms_')) or name.endswith('_offset') or self._trunk32(name) or name == 'conv1':
+                continue                                    # consumed in other layouts (relation_bwd kernels, padded DCN offset convs; float32 trunk);
+                                                            # conv1 reads the image: no data gradient
             if name.startswith(('qk_', 'linear_out_')):     # [Wq; Wk]^T | Wout^T side by side: the [1024, 3072] operand of the ONE
                 i = name.rsplit('_', 1)[1]                  # projection-backward GEMM of relation module i (relation.GradSink)
                 group = ('rel_cat_' + i, 0 if name.startswith('qk_') else self.W.slices['qk_' + i][1][0])
@@ -379,7 +416,7 @@ class Trainer(object):
 
     # ---- accessors ----------------------------------------------------------------------------------------
     def _trunk32(self, name):
-        return self.trunk_fp32 and name.startswith('res') and not name.endswith('_offset')
+        return self.trunk_fp32 and (name.startswith('res') or name == 'conv1') and not name.endswith('_offset')
 
     def w(self, name):          # bf16 working copy (the float32 master weights for the trunk layers of a cfg.trunk_fp32 trainer)
         return self.W.view(self.W.master if self._trunk32(name) else self.W.work, name)
@@ -750,12 +787,15 @@ class Trainer(object):
             half = res4[len(res4) // 2]                                        # '4b11' of 4a, 4b1 .. 4b22
             cuts = [0, first('res4'), first('res' + half + '_'), first('res5'), trunk_end, self.W.size]
             self._bucket_names = ('res3', 'res4_lo', 'res4_hi', 'res5', 'heads')
+            if self.res2_trainable:         # conv1 (when trainable) + res2 in front of res3: bucket 0, the last one the backward pass announces
+                cuts = [0, first('res3')] + cuts[1:]
+                self._bucket_names = ('res2',) + self._bucket_names
             assert cuts == sorted(set(cuts)), cuts
             self._bucket_cuts = cuts
             self._unit_bucket = {}
             hi = False
             for u in self.units:
-                if u[0] < 3:
+                if u[0] < 3 and not self.res2_trainable:
                     continue
                 if u[0] == 4:
                     hi = hi or (u[1] == half)
