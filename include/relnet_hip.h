@@ -140,7 +140,7 @@ void relnet_gemm_debug_phase_ts(void* buf); /* measurement knob: the ring kernel
                                              * wall clock (100 MHz) at entry / k-loop start / k-loop end / exit, [4] = shader cycles entry -> k-loop end;
                                              * NULL (default) = off.  tools/tile_phase_probe.py */
 void relnet_gemm_debug_ablate(int a);     /* measurement knob for tile 8: 1 = fill path only, 2 = LDS + MFMA only (garbage results) */
-void relnet_chain_debug(int flags);        /* measurement knob for chain256_roles_kernel (garbage results while non-zero): 1 = half of the weight loads, 2 = none, 4 = no shortcut-slice loads, 8 = no global stores */
+void relnet_chain_debug(int flags);        /* measurement knob for chain256_roles_kernel (garbage results while non-zero): 1 = half of the weight loads (W3 LDS-DMA pieces and W1' register loads), 2 = none, 4 = no shortcut-slice loads, 8 = no global stores */
 int relnet_gemm_tile_count(void);         /* number of tile configurations (valid relnet_gemm_force_tile values 1..count) */
 int relnet_gemm_last_launch(void);        /* what the last bf16-operand relnet_gemm_nt / relnet_conv2d_nhwc(_wf) launch ran, for tests: low byte 1 = LDS-tiled,
                                            * 2 = ring, 3 = ring with the window schedule, 4 = ring with a hand-scheduled k-loop, 5 = row panel, 6 = split-K;

@@ -49,7 +49,7 @@ struct ChainArgs {
   int P;
   int H, W, Ho, Wo;           // GATHER: the full map x addresses and the compact one (Ho = (H - 1) / 2 + 1, Wo likewise); P = B * Ho * Wo
   int dbg;                    // timing ablations of chain256_roles_kernel (relnet_chain_debug; results are then WRONG): 1 = half of the weight
-                              // loads, 2 = no weight loads, 4 = no shortcut-slice loads, 8 = no global stores
+                              // loads (W3 pieces and W1' register loads), 2 = no weight loads, 4 = no shortcut-slice loads, 8 = no global stores
 };
 
 // One kernel for both widths, in passes of 64 output channels of the expand product:
@@ -291,33 +291,56 @@ __global__ __launch_bounds__(512) void bottleneck_chain_kernel(ChainArgs a) {
 
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// res4 form of the two-product chain (MID = 256: 256 -> 1024 + shortcut + ReLU, then the next unit's 1024 -> 256 + ReLU), r04,
-// with ONE ROLE PER WAVEFRONT.  Every wavefront doing everything (bottleneck_chain_kernel's structure with the passes cut in two
-// 32-channel steps so that the weight slots stay 32 KB: built and measured first) needs 64 (mid2 fragments) + 128 (mid1'
-// accumulators) + 16 registers of essential state per wavefront of 256: the compiler spilled the address arithmetic of the activation
-// loads into the step loop
-// (a scratch reload -> s_waitcnt vmcnt(0) between every two HBM loads) and had one register set left for weight fragments (ds_read ->
-// lgkmcnt(0) -> MFMA, 32 times per step): 21.6 ms per 54-image step against 20.0 ms with this kernel on the same box (the two
-// separate launches: 22.0).  Here a workgroup walks sets of FOUR 32-pixel tiles; tile T belongs to two wavefronts:
-//   A-wave T      expand product of step g (16 MFMAs: W3 rows [32 g', +32) x mid2 fragments in registers), bias + shortcut + ReLU into
-//                 the tile's stage buffer, and the stores of finished slices (they drain in the background: an A-wave never waits on vmcnt
-//                 except for its mid2 fragments once per tile);
-//   B-wave T + 4  reduce product of step g - 1 (16 MFMAs: the 32 channels the A-wave finished one step earlier, read back from the
-//                 stage buffer, x the matching W1' fragments) into 128 accumulator registers; mid1' out once per tile.
-// B-waves 4, 5 also stream the weights (W3 of step g + 1 and W1' of step g into the slot not in use: vmcnt(0) per step, L2 hits);
-// B-waves 6, 7 load the shortcut slices of all four tiles TWO passes ahead into a four-deep stage ring per tile and wait with a
-// COUNTED vmcnt (only loads in their queue: in-order), so HBM loads have two passes and HBM stores unlimited time to complete.
-// One s_barrier per step (32 channels); same passes, rounding points and results as the one-role form.
-// What bounds it (r04, 54 images, 209 us per launch = 1.63 us per step): the L2 -> LDS fill path.  Every workgroup streams the full
-// 1 MB of W3 + W1' per set of four tiles -- 1.0 GB per launch, + 0.27 GB of shortcut slices through the same path -- at the 5.5 - 6 TB/s
-// that path sustains (tools/fill_probe.py); HBM carries 0.66 GB (3.2 TB/s).  Eight tiles per set would halve the weight stream, but
-// their mid1' accumulators alone are all the registers four B-waves have.
-// LDS: weights 2 x 32 KB | stage 4 tiles x 4 x 4 KB | mid1' staging 4 x 4 KB | biases 5 KB = 149 KB.
+// res4 form of the two-product chain (MID = 256: 256 -> 1024 + shortcut + ReLU, then the next unit's 1024 -> 256 + ReLU), with ONE ROLE
+// PER WAVEFRONT.  Every wavefront doing everything (bottleneck_chain_kernel's structure) needs 64 (mid2 fragments) + 128 (mid1'
+// accumulators) + 16 registers of essential state per wavefront of 256 and spilled into the step loop (r04: 21.6 ms per 54-image step
+// against 20.0 ms with roles).  Here a workgroup walks sets of FOUR 32-pixel tiles in lock step, one s_barrier per STEP = PASS = 64
+// output channels of the expand product, 16 steps per set:
+//   A-wave T (0..3)   tile T.  mid2 fragments once per tile (registers).  Step s: two independent accumulators (W3 rows [64 p, +32) and
+//                     [64 p + 32, +32), fragments from the weight slot s & 1 in four batches through two register sets, ks = 0..15 each,
+//                     MFMAs interleaved, at raised priority on the pipe the wave shares with a B-wave), bias + shortcut + ReLU of
+//                     both halves in place into the tile's stage buffer s % 4, then the finished slice of pass s - 1 (fenced by the barrier
+//                     at the top of the step; the B-waves only read it) goes out as 16-byte coalesced rows.  The stores drain in the
+//                     background: an A-wave waits on vmcnt only for its mid2 fragments, once per tile.
+//   B-wave b (4 + b)  mid1' channels [64 b, +64) of ALL FOUR tiles: 4 tiles x 2 row tiles x 16 accumulator registers.  Step s consumes
+//                     pass s - 1: the slices the A-waves finished before the barrier, read back from the four stage rings, x the eight W1'
+//                     fragments (rt = 2 b + {0, 1}, k-step 4 p + kk).  Per accumulator the MFMA order is pass ascending, then kk = 0..3.
+//                     W1' never enters LDS: a fragment (1 KB, fragment-major in w1f, an L2 hit) is loaded by global_load_dwordx4 into this
+//                     wave's registers, ONE register set: the successor (same rt, kk of the next pass) is requested right after the
+//                     fragment's fourth MFMA of the step (kk outer, tile inner) and has the rest of the step to arrive.  mid1' leaves at a
+//                     tile's last pass: bias + ReLU + transpose through the wave's 4 KB buffer, tile by tile, to m1 + row * 256 + 64 b.
+// The B-waves are also the loaders, twelve LDS-DMA pieces each per step, issued right after the barrier: W3 of pass s + 1 (32 pieces into
+// slot (s + 1) & 1: waves 4, 5 twelve each, waves 6, 7 four each) and, on waves 6 and 7, the shortcut slices of pass s + 2 of two tiles
+// each (8 pieces) into stage buffer (s + 2) % 4 -- the buffer whose store-out was read at step s - 1; live buffers are {s - 1, s, s + 1,
+// s + 2}.
+// vmcnt by hand (only loads in a B-wave's queue, so they retire in order; none of them is visible to the compiler's wait-count pass):
+//   queue of a step   [12 DMA pieces: W3 first, then shortcut] [8 W1' fragments, in the order they are consumed]
+//   top of a step     W3 of this step must be in LDS before the barrier: vmcnt(8) on waves 4, 5 and vmcnt(16) on waves 6, 7 (the W1'
+//                     fragments, and the shortcut pieces behind the four W3 pieces, stay in flight);
+//   fragment j        behind it: 7 - j older fragments, this step's 12 pieces, the j successors already requested: vmcnt(19), always.  The
+//                     newest DMA pieces stay in flight across it; the shortcut slice of pass s + 1 is forced by the first of these waits
+//                     of step s, one step after its request.
+//   after mid1' rows  stores retire out of order with loads: the next top-of-step wait is vmcnt(0) (`drain`).
+// The loads of the last steps run past the end (W3 / W1' wrap to pass 0, shortcut rows clamp to pixel P - 1, nobody reads them) so that
+// the counts hold everywhere; a final vmcnt(0) keeps LDS-DMA from landing after the workgroup has ended.
+// In place (x_next over the shortcut operand): every (pixel, 64-channel slice) is loaded (request at step s - 2, in LDS by step s) before
+// it is stored (step s + 1), and no other workgroup touches those pixels.
+// Same passes, k order per accumulator, rounding points and hence the same bits as the 32-channel-step form it replaces (r25;
+// tests/test_gpu_chain256_bits.py) and as the one-role kernel.
+// LDS: W3 slots 2 x 32 KB | stage 4 tiles x 4 x 4 KB | mid1' staging 4 x 4 KB | biases 5 KB = 149 KB.
 // ---------------------------------------------------------------------------------------------------------------------------
+// One W1' fragment into registers, from inline assembly (uniform base + 16 bytes per lane): the compiler's wait-count pass does not see it,
+// so it puts no vmcnt(0) in front of the LDS-DMA prefetch.  The destination counts as written at once: every consumer sits behind a
+// counted wait that names the registers (chain_wait_frag).  (s_nop 4: the base may come fresh from a v_readfirstlane.)
+__device__ __forceinline__ void chain_gld16(bf16x8& d, const void* sbase, unsigned voff) {
+  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=v"(d) : "v"(voff), "s"(sbase) : "memory");
+}
+__device__ __forceinline__ void chain_wait_frag(bf16x8& d) { asm volatile("s_waitcnt vmcnt(19)" : "+v"(d) : : "memory"); }
+
 constexpr int kRolesLdsBytes = 2 * 32768 + 4 * 4 * 4096 + 4 * 4096 + (1024 + 256) * 4;      // weights | stage rings | mid1' staging | biases
 __global__ __launch_bounds__(512) void chain256_roles_kernel(ChainArgs a) {
-  constexpr int MID = 256, COUT = 4 * MID, KS = MID / 16, RT = MID / 32, NP = COUT / 64, NSTEP = 2 * NP, NTL = 4, NBUF = 4;
-  constexpr int W3P = KS * 1024, W1P = 2 * RT * 1024, SLOT = W3P + W1P, WBYTES = 2 * SLOT;
+  constexpr int MID = 256, COUT = 4 * MID, KS = MID / 16, NP = COUT / 64, NTL = 4, NBUF = 4;
+  constexpr int SLOT = 2 * KS * 1024, WBYTES = 2 * SLOT;         // a slot: the 32 W3 fragments of a pass (two row tiles x 16 k-steps)
   constexpr int STG = NBUF * 4096, M1S = WBYTES + NTL * STG, BIAS = M1S + NTL * 4096;
   static_assert(BIAS + (COUT + MID) * 4 == kRolesLdsBytes, "host launch and kernel disagree on the LDS layout");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -332,9 +355,9 @@ __global__ __launch_bounds__(512) void chain256_roles_kernel(ChainArgs a) {
   const int ntile = (a.P + 31) / 32, nset = (ntile + NTL - 1) / NTL;
   const int n_iter = (nset - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;      // (idle tiles of the last set still take part)
   if (n_iter <= 0) return;
-  const int G = n_iter * NSTEP, NPASS = n_iter * NP;            // steps / passes of this workgroup
+  const int G = n_iter * NP;                                    // steps = passes of this workgroup
   auto tile_p0 = [&](int it, int T) { return (((int)blockIdx.x + it * (int)gridDim.x) * NTL + T) * 32; };     // >= P for idle tiles: loads clamp, stores are masked
-  // shortcut slice of global pass Pg for tile T -> stage buffer Pg % NBUF
+  // shortcut slice of global pass Pg for tile T -> stage buffer Pg % NBUF (4 pieces)
   auto issue_x = [&](int T, int Pg) {
     if (a.dbg & 4) return;
     const int p0 = tile_p0(Pg / NP, T), p = Pg % NP;
@@ -346,26 +369,20 @@ __global__ __launch_bounds__(512) void chain256_roles_kernel(ChainArgs a) {
       chain_glds16((const unsigned char*)a.x + off, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(sb - smem) + i * 1024));
     }
   };
-  // weights of the slot step g + 1 reads: W3 rows of step g + 1 (fragments 0..15) and W1' k-steps of step g (fragments 16..31); loader l of 2
-  auto issue_w = [&](int g, int l) {
+  // W3 of pass g + 1 into slot (g + 1) & 1: B-wave b's share of its 32 pieces (waves 4, 5: twelve each, waves 6, 7: four each)
+  auto issue_w3 = [&](int g, int b) {
     if (a.dbg & 2) return;
-    unsigned char* wb = smem + ((g + 1) & 1) * SLOT;
-    const int s3 = (g + 1) % NSTEP, s1 = g % NSTEP;
+    const int first = b < 2 ? 12 * b : 16 + 4 * b, n = b < 2 ? 12 : 4;
+    const unsigned lb = lds0 + (unsigned)(((g + 1) & 1) * SLOT);
+    const unsigned char* src = (const unsigned char*)a.w3f + (unsigned)(((g + 1) % NP) * SLOT) + lane * 16u;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      if ((a.dbg & 1) && (i & 1)) continue;
-      const int q = l + 2 * i;
-      if (q < KS) {
-        if (g + 1 < G)
-          chain_glds16((const unsigned char*)a.w3f + ((unsigned)((s3 * KS + q) * 1024) + lane * 16u), __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(wb - smem) + q * 1024));
-      } else if (g >= 0 && g < G) {
-        const int q1 = q - KS, rt = q1 >> 1, j = q1 & 1;
-        chain_glds16((const unsigned char*)a.w1f + ((unsigned)((rt * (COUT / 16) + (s1 >> 1) * 4 + (s1 & 1) * 2 + j) * 1024) + lane * 16u), __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(wb - smem) + W3P + q1 * 1024));
-      }
+    for (int i = 0; i < 12; ++i) {
+      if (i >= n || ((a.dbg & 1) && (i & 1))) continue;
+      chain_glds16(src + (first + i) * 1024, __builtin_amdgcn_readfirstlane(lb + (unsigned)((first + i) * 1024)));
     }
   };
-  // prologue: W3 of step 0 (both weight loaders: their share of slot 0), shortcut slices of passes 0 and 1
-  if (wave == 4 || wave == 5) issue_w(-1, wave - 4);
+  // prologue: W3 of pass 0, shortcut slices of passes 0 and 1
+  if (wave >= 4) issue_w3(-1, wave - 4);
   if (wave >= 6) {
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) { issue_x(2 * (wave - 6) + tt, 0); }
@@ -379,47 +396,71 @@ __global__ __launch_bounds__(512) void chain256_roles_kernel(ChainArgs a) {
     const int T = wave;
     unsigned char* const stg = smem + WBYTES + T * STG;
     bf16x8 m2f[KS];
+    __builtin_amdgcn_s_setprio(2);         // the A-wave's MFMAs go first on the pipe it shares with a B-wave: its epilogue then runs under the B-wave's
 #pragma unroll 1
-    for (int g = 0; g <= G + 1; ++g) {
+    for (int g = 0; g <= G; ++g) {
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // (this wave's stage writes of the previous step are in LDS)
       if (g < G) {
-        const int st = g % NSTEP, p = st >> 1, ct = st & 1, Pg = g >> 1;
-        if (st == 0) {
-          const int px = min(tile_p0(g / NSTEP, T) + l31, a.P - 1);
+        const int p = g % NP;
+        if (p == 0) {
+          const int px = min(tile_p0(g / NP, T) + l31, a.P - 1);
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) m2f[ks] = *(const bf16x8*)(a.m2 + (long)px * MID + 16 * ks + 8 * half);
           __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0) HERE, once per tile, as a real instruction the compiler's wait-count pass sees: left to it (or
                                                    // hidden in an asm statement) counted vmcnt waits land on the main path of every step and drain the stores
         }
         const uint4* w3 = (const uint4*)(smem + (g & 1) * SLOT);
-        // all sixteen weight fragments of the step up front (64 registers this role has to spare): the expand product is ONE dependent
-        // MFMA chain (measured: the step time does not depend on it -- see the bound below -- but the MFMA pipe is released earlier)
-        bf16x8 wf[KS];
+        unsigned char* sb = stg + (g % NBUF) * 4096;
+        uint2 xv[2][4];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) wf[ks] = *(const bf16x8*)&w3[ks * 64 + lane];
-        unsigned char* sb = stg + (Pg % NBUF) * 4096;
-        uint2 xv[4];
+        for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int gq = 0; gq < 4; ++gq) xv[gq] = *(const uint2*)(sb + l31 * 128 + (((ct * 4 + gq) ^ ((l31 >> 1) & 7)) << 4) + 8 * half);
-        __builtin_amdgcn_sched_barrier(0);                   // (the scheduler otherwise sinks the reads back between the MFMAs)
-        f32x16 ac;
+          for (int gq = 0; gq < 4; ++gq) xv[ct][gq] = *(const uint2*)(sb + l31 * 128 + (((ct * 4 + gq) ^ ((l31 >> 1) & 7)) << 4) + 8 * half);
+        // two independent chains of sixteen MFMAs (rows [64 p, +32) and [64 p + 32, +32)), interleaved.  The 32 weight fragments come in four
+        // batches (4 k-steps x 2 chains) through two register sets, a batch requested two batches ahead of its MFMAs: left to itself the
+        // scheduler reads two fragments at a time and waits for LDS between every two MFMAs.
+        f32x16 ac[2];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) ac[r] = 0.f;
+        for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-          ac = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], m2f[ks], ac, 0, 0, 0);
+          for (int r = 0; r < 16; ++r) ac[ct][r] = 0.f;
+        bf16x8 wf[2][8];
+        auto read_w3 = [&](int set, int bt) {
 #pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          uint2* sp = (uint2*)(sb + l31 * 128 + (((ct * 4 + gq) ^ ((l31 >> 1) & 7)) << 4) + 8 * half);
-          const float4 bv = *(const float4*)(sB3 + p * 64 + ct * 32 + 8 * gq + 4 * half);
-          const float v0 = fmaxf(ac[4 * gq + 0] + bv.x + bf2f(xv[gq].x & 0xffff), 0.f), v1 = fmaxf(ac[4 * gq + 1] + bv.y + bf2f(xv[gq].x >> 16), 0.f);
-          const float v2 = fmaxf(ac[4 * gq + 2] + bv.z + bf2f(xv[gq].y & 0xffff), 0.f), v3 = fmaxf(ac[4 * gq + 3] + bv.w + bf2f(xv[gq].y >> 16), 0.f);
-          *sp = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) wf[set][2 * i + ct] = *(const bf16x8*)&w3[(ct * KS + 4 * bt + i) * 64 + lane];
+        };
+        read_w3(0, 0);
+        read_w3(1, 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int bt = 0; bt < 4; ++bt) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) ac[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[bt & 1][2 * i + ct], m2f[4 * bt + i], ac[ct], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (bt + 2 < 4) {
+            read_w3(bt & 1, bt + 2);
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+          for (int gq = 0; gq < 4; ++gq) {
+            uint2* sp = (uint2*)(sb + l31 * 128 + (((ct * 4 + gq) ^ ((l31 >> 1) & 7)) << 4) + 8 * half);
+            const float4 bv = *(const float4*)(sB3 + p * 64 + ct * 32 + 8 * gq + 4 * half);
+            const uint2 x2 = xv[ct][gq];
+            const float v0 = fmaxf(ac[ct][4 * gq + 0] + bv.x + bf2f(x2.x & 0xffff), 0.f), v1 = fmaxf(ac[ct][4 * gq + 1] + bv.y + bf2f(x2.x >> 16), 0.f);
+            const float v2 = fmaxf(ac[ct][4 * gq + 2] + bv.z + bf2f(x2.y & 0xffff), 0.f), v3 = fmaxf(ac[ct][4 * gq + 3] + bv.w + bf2f(x2.y >> 16), 0.f);
+            *sp = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+          }
       }
-      if ((g & 1) && g >= 3) {
-        // slice Pf is complete (A: step 2 Pf + 1) and consumed (B: step 2 Pf + 2): out, 16-byte coalesced rows
-        const int Pf = (g - 3) >> 1, p0 = tile_p0(Pf / NP, T), p = Pf % NP;
+      if (g >= 1) {
+        // the slice of pass g - 1 is complete (this wave, step g - 1, fenced by the barrier above): out, 16-byte coalesced rows
+        const int Pf = g - 1, p0 = tile_p0(Pf / NP, T), p = Pf % NP;
         const unsigned char* sb = stg + (Pf % NBUF) * 4096 + lane * 16;
         const uint4 v0 = *(const uint4*)sb, v1 = *(const uint4*)(sb + 1024), v2 = *(const uint4*)(sb + 2048), v3 = *(const uint4*)(sb + 3072);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -431,86 +472,124 @@ __global__ __launch_bounds__(512) void chain256_roles_kernel(ChainArgs a) {
       }
     }
   } else {
-    // ================================================= B-wave: tile T = wave - 4 =============================================
-    const int T = wave - 4;
-    const unsigned char* const stg = smem + WBYTES + T * STG;
-    unsigned char* const m1s = smem + M1S + T * 4096;
-    f32x16 m1acc[RT];
+    // ================================================= B-wave b = wave - 4: mid1' channels [64 b, +64) of the four tiles =========
+    const int b = wave - 4;
+    unsigned char* const m1s = smem + M1S + b * 4096;
+    const unsigned lrd = (unsigned)(l31 * 128 + 8 * half) | (unsigned)(((l31 >> 1) & 7) << 4);      // stage read: chunk c of this lane's row at lrd ^ (c << 4)
+    const unsigned voff = lane * 16u;
+    f32x16 m1acc[NTL][2];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+    for (int T = 0; T < NTL; ++T)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) m1acc[rt][r] = 0.f;
+      for (int r2 = 0; r2 < 2; ++r2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m1acc[T][r2][r] = 0.f;
+    bf16x8 wf[8];                            // W1' fragments of the pass in hand, j = 2 kk + r2: (rt = 2 b + r2, k-step 4 p + kk)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wf[j] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    auto load_w1 = [&](int j, int pass) {
+      if ((a.dbg & 2) || ((a.dbg & 1) && (j & 1))) return;
+      chain_gld16(wf[j], (const unsigned char*)a.w1f + (unsigned)((((2 * b + (j & 1)) * (COUT / 16)) + 4 * pass + (j >> 1)) * 1024), voff);
+    };
     bool drain = false;                      // this wave has stores in its queue (mid1' rows): the next counted wait must be a full one
+    // step 0 (nothing to consume yet) stands outside the loop: the same queue as every step, the fragments of pass 0 in the place of the
+    // successors.  (As a branch of the loop body it made the register allocator copy and spill the accumulators around every MFMA.)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    issue_w3(0, b);
+    if (wave >= 6) {
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) issue_x(2 * (wave - 6) + tt, 2);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) load_w1(j, 0);
 #pragma unroll 1
-    for (int g = 0; g <= G + 1; ++g) {
-      if (wave < 6) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // weights of step g (and of B's step g - 1) landed
-      else if (!(g & 1) && (g >> 1) < NPASS) {                                           // slice of pass g / 2 landed; the next one may be in flight
-        if (!drain && (g >> 1) + 1 < NPASS) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        drain = false;
-      }
+    for (int g = 1; g <= G; ++g) {
+      // W3 of pass g (requested at step g - 1, ahead of the W1' fragments and, on waves 6 and 7, of eight shortcut pieces) has landed
+      if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      else if (wave < 6) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      drain = false;
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (wave < 6) issue_w(g, wave - 4);
-      else if (!(g & 1) && (g >> 1) + 2 < NPASS) {
+      const int q = g - 1, p = q % NP, pn = g % NP;            // the pass the A-waves finished before this barrier; the pass after it
+      const unsigned char* sb = smem + WBYTES + (q % NBUF) * 4096;
+      // x_next fragments of the four tiles, 16 channels (kk) at a time: the halves of kk + 1 are requested before the MFMAs of kk and
+      // joined after them (the counted lgkmcnt waits are the compiler's)
+      uint2 xr[NTL][2];
+      bf16x8 xf[NTL];
+      unsigned tb[NTL];                                        // tile bases the compiler cannot relate: it would pair the reads of two tiles
+#pragma unroll                                                 // (ds_read2st64) and move every half into place behind a full wait, ahead of the MFMAs
+      for (int T = 0; T < NTL; ++T) { tb[T] = (unsigned)(T * STG); asm volatile("" : "+v"(tb[T])); }
+      auto read_x = [&](int kk) {
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) issue_x(2 * (wave - 6) + tt, (g >> 1) + 2);
+        for (int T = 0; T < NTL; ++T) {
+          xr[T][0] = *(const uint2*)(sb + tb[T] + (lrd ^ (unsigned)((2 * kk) << 4)));
+          xr[T][1] = *(const uint2*)(sb + tb[T] + (lrd ^ (unsigned)((2 * kk + 1) << 4)));
+        }
+      };
+      auto join_x = [&]() {
+#pragma unroll
+        for (int T = 0; T < NTL; ++T) { *(uint2*)&xf[T] = xr[T][0]; *((uint2*)&xf[T] + 1) = xr[T][1]; }
+      };
+      read_x(0);                                               // (ahead of the DMA issue: it arrives behind it)
+      __builtin_amdgcn_sched_barrier(0);
+      issue_w3(g, b);
+      if (wave >= 6) {
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) issue_x(2 * (wave - 6) + tt, g + 2);
       }
-      if (g >= 1 && g <= G) {
-        const int h = g - 1, st = h % NSTEP, ct = st & 1, Pg = h >> 1;                 // the step the A-wave finished before this barrier
-        const uint4* w1 = (const uint4*)(smem + (g & 1) * SLOT + W3P);
-        const unsigned char* sb = stg + (Pg % NBUF) * 4096;
-        bf16x8 xf[2];
+      join_x();
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          *(uint2*)&xf[j] = *(const uint2*)(sb + l31 * 128 + (((ct * 4 + 2 * j) ^ ((l31 >> 1) & 7)) << 4) + 8 * half);
-          *((uint2*)&xf[j] + 1) = *(const uint2*)(sb + l31 * 128 + (((ct * 4 + 2 * j + 1) ^ ((l31 >> 1) & 7)) << 4) + 8 * half);
-        }
-        bf16x8 wf[2][RT];                                      // (all sixteen fragments up front, as in the A-wave)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) wf[j][rt] = *(const bf16x8*)&w1[(rt * 2 + j) * 64 + lane];
+      for (int kk = 0; kk < 4; ++kk) {
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt)
-            m1acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][rt], xf[j], m1acc[rt], 0, 0, 0);
-        if (st == NSTEP - 1) {
-          // mid1' = relu(. + b1) of the tile that just ended, 64 channels at a time through this wave's staging buffer
-          const int p0 = tile_p0(h / NSTEP, T);
-#pragma unroll
-          for (int hc = 0; hc < RT / 2; ++hc) {
-#pragma unroll
-            for (int r2 = 0; r2 < 2; ++r2)
-#pragma unroll
-              for (int gq = 0; gq < 4; ++gq) {
-                const int rt = 2 * hc + r2;
-                const float4 bv = *(const float4*)(sB1 + rt * 32 + 8 * gq + 4 * half);
-                const float v0 = fmaxf(m1acc[rt][4 * gq + 0] + bv.x, 0.f), v1 = fmaxf(m1acc[rt][4 * gq + 1] + bv.y, 0.f);
-                const float v2 = fmaxf(m1acc[rt][4 * gq + 2] + bv.z, 0.f), v3 = fmaxf(m1acc[rt][4 * gq + 3] + bv.w, 0.f);
-                *(uint2*)(m1s + l31 * 128 + (((r2 * 4 + gq) ^ ((l31 >> 1) & 7)) << 4) + 8 * half) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
-              }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            const unsigned char* sl = m1s + lane * 16;
-            const uint4 v0 = *(const uint4*)sl, v1 = *(const uint4*)(sl + 1024), v2 = *(const uint4*)(sl + 2048), v3 = *(const uint4*)(sl + 3072);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            auto put = [&](int i, const uint4& v) {
-              const int row = 8 * i + drow;
-              if (p0 + row < a.P && !(a.dbg & 8)) *(uint4*)(a.m1 + (long)(p0 + row) * MID + hc * 64 + ((dslot ^ ((row >> 1) & 7)) << 3)) = v;
-            };
-            put(0, v0); put(1, v1); put(2, v2); put(3, v3);
-          }
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) m1acc[rt][r] = 0.f;
-          drain = true;
+        if (kk + 1 < 4) {
+          read_x(kk + 1);
+          __builtin_amdgcn_sched_barrier(0);
         }
+#pragma unroll
+        for (int r2 = 0; r2 < 2; ++r2) {
+          const int j = 2 * kk + r2;
+          chain_wait_frag(wf[j]);
+#pragma unroll
+          for (int T = 0; T < NTL; ++T) m1acc[T][r2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j], xf[T], m1acc[T][r2], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);                   // (the four MFMAs have issued: the registers may be requested again)
+          load_w1(j, pn);
+        }
+        if (kk + 1 < 4) join_x();
+      }
+      if (p == NP - 1) {
+        // mid1' = relu(. + b1) of the four tiles that just ended, one tile (32 px x this wave's 64 channels) at a time through the staging buffer
+#pragma unroll
+        for (int T = 0; T < NTL; ++T) {
+          const int p0 = tile_p0(q / NP, T);
+#pragma unroll
+          for (int r2 = 0; r2 < 2; ++r2)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+              const float4 bv = *(const float4*)(sB1 + (2 * b + r2) * 32 + 8 * gq + 4 * half);
+              const float v0 = fmaxf(m1acc[T][r2][4 * gq + 0] + bv.x, 0.f), v1 = fmaxf(m1acc[T][r2][4 * gq + 1] + bv.y, 0.f);
+              const float v2 = fmaxf(m1acc[T][r2][4 * gq + 2] + bv.z, 0.f), v3 = fmaxf(m1acc[T][r2][4 * gq + 3] + bv.w, 0.f);
+              *(uint2*)(m1s + l31 * 128 + (((r2 * 4 + gq) ^ ((l31 >> 1) & 7)) << 4) + 8 * half) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+            }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+          const unsigned char* sl = m1s + lane * 16;
+          const uint4 v0 = *(const uint4*)sl, v1 = *(const uint4*)(sl + 1024), v2 = *(const uint4*)(sl + 2048), v3 = *(const uint4*)(sl + 3072);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+          auto put = [&](int i, const uint4& v) {
+            const int row = 8 * i + drow;
+            if (p0 + row < a.P && !(a.dbg & 8)) *(uint4*)(a.m1 + (long)(p0 + row) * MID + b * 64 + ((dslot ^ ((row >> 1) & 7)) << 3)) = v;
+          };
+          put(0, v0); put(1, v1); put(2, v2); put(3, v3);
+#pragma unroll
+          for (int r2 = 0; r2 < 2; ++r2)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) m1acc[T][r2][r] = 0.f;
+        }
+        drain = true;
       }
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // no LDS-DMA piece may land after the workgroup has ended
   }
 }
 
