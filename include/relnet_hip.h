@@ -49,6 +49,18 @@ int relnet_proposal_decode(const float* cls_prob, const long* cls_strides4, cons
  * Equal scores are ordered by descending index (the reference's argsort is unstable).            */
 int relnet_topk_sort(const float* scores, const float* boxes, float* out_boxes5, int* out_index,
                      int* out_count, int B, int n, int K, void* stream);
+/* relnet_topk_sort_large (proposal.py:140-144): the same order, tie rule and outputs for any 0 < K <= n < 65536, i.e. the
+ * TEST.PROPOSAL_PRE_NMS_TOP_N 20000 / TRAIN.RPN_PRE_NMS_TOP_N 12000 of the experiment files, which relnet_topk_sort's single
+ * 64 KiB LDS sort cannot hold.  Two launches, no host synchronisation, capturable: index ranges of 8192 anchors sorted in LDS
+ * into `workspace`, then one thread per key finds its global rank (position in its range + binary searches in the others; the
+ * composite keys are distinct, so the ranks are a permutation) and rows with rank < K are written.  For K <= 8192 the bits
+ * equal relnet_topk_sort's.  -inf rows inside the top K come in their tie order with score -inf; out_count = finite scores
+ * among the first K.  workspace: 8-byte aligned, workspace_bytes >= relnet_topk_sort_large_workspace_bytes(B, n) (-1 for a
+ * shape the entry refuses); it needs no initialisation and is free again when the launches have run.  Anything else is
+ * refused before a launch.                                                                                                   */
+long relnet_topk_sort_large_workspace_bytes(int B, int n);   /* proposal.py:140-144: scratch of the order for K > 8192 */
+int relnet_topk_sort_large(const float* scores, const float* boxes, float* out_boxes5, int* out_index, int* out_count,
+                           int B, int n, int K, void* workspace, long workspace_bytes, void* stream);
 /* nms_kernel.cu:34-78 (bitmask, upper triangle only); mask [B, n, ceil(n/64)] uint64              */
 int relnet_nms_mask(const float* boxes5, const int* counts /*[B] or NULL*/, unsigned long long* mask,
                     int B, int n, int n_stride, float thresh, void* stream);

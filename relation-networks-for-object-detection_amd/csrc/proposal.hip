@@ -6,6 +6,9 @@
 //                           float64 exactly like the numpy reference, cast to float32.
 //   topk_sort_kernel        descending top-K of the scores: 48-bit radix select of the
 //                           K-th key, compaction, bitonic sort in LDS (one workgroup / image).
+//   topk_chunk_sort_kernel, topk_rank_gather_kernel
+//                           the same order for K past the LDS capacity (8192 < K <= n): index ranges of 8192 sorted in
+//                           LDS, then each key's global rank by binary searches in the other ranges.
 //   nms_mask_kernel         64x64 IoU tiles -> uint64 suppression bitmask (upper triangle).
 //   nms_scan_kernel         greedy scan on device (the reference copies 4.5 MB of mask to
 //                           the host and scans serially), early exit at post_nms_top_n,
@@ -186,6 +189,88 @@ __global__ __launch_bounds__(kSortThreads) void topk_sort_kernel(TopkArgs g) {
   if (lane == 0 && valid) atomicAdd(&s_valid, valid);
   __syncthreads();
   if (tid == 0) g.out_count[b] = s_valid;
+}
+
+// ---------------------------------------------------------------------------------------
+// top-K past the LDS capacity (K up to n < 65536; TEST.PROPOSAL_PRE_NMS_TOP_N is 20000): the same composite keys, the same
+// order, in two launches.  160 KiB of LDS cannot hold 20000 eight-byte keys padded to a power of two, so
+//   topk_chunk_sort_kernel   cuts the anchors into index ranges of kSortCap; workgroup (chunk, image) sorts its range
+//                            descending in LDS (the bitonic stage above) and writes it to the caller's workspace;
+//   topk_rank_gather_kernel  one thread per key: its rank among all n keys = its position in its own chunk + for each of the at
+//                            most 7 other chunks the number of keys above it (binary search; the keys are distinct, so the
+//                            ranks are a permutation of 0..n-1).  rank < K writes row `rank`: no selection pass.
+// Every chunk is sorted whatever K is: the cut is not known before the ranks are.  The grids depend on (B, n) only.
+// ---------------------------------------------------------------------------------------
+constexpr int kMaxChunks = 8;        // ceil(65535 / kSortCap)
+constexpr int kRankThreads = 256;
+
+struct TopkLargeArgs {
+  TopkArgs t;
+  unsigned long long* sorted;        // [B, nchunks, kSortCap] workspace: chunk c's first min(n - c kSortCap, kSortCap) words are written
+  int nchunks;
+};
+
+__global__ __launch_bounds__(kSortThreads) void topk_chunk_sort_kernel(TopkLargeArgs g) {
+  __shared__ unsigned long long keys[kSortCap];
+  const int tid = threadIdx.x, c = blockIdx.x, b = blockIdx.y;
+  const int base = c * kSortCap;
+  const int cnt = min(g.t.n - base, kSortCap);
+  const float* sc = g.t.scores + (long)b * g.t.n + base;
+  int np2 = 1;
+  while (np2 < cnt) np2 <<= 1;
+  for (int i = tid; i < np2; i += kSortThreads)      // the tail sorts last (a real key is 0 only for index 0, and then it IS last)
+    keys[i] = i < cnt ? (((unsigned long long)order_key(sc[i]) << 16) | (unsigned int)(base + i)) : 0ull;
+  if (c == 0 && tid == 0) g.t.out_count[b] = 0;      // the second launch counts into it
+  __syncthreads();
+  bitonic_sort_desc_pairs<kSortThreads>(keys, np2);
+  unsigned long long* out = g.sorted + ((long)b * g.nchunks + c) * kSortCap;
+  for (int i = tid; i < cnt; i += kSortThreads) out[i] = keys[i];
+}
+
+__global__ __launch_bounds__(kRankThreads) void topk_rank_gather_kernel(TopkLargeArgs g) {
+  constexpr int kBlocksPerChunk = kSortCap / kRankThreads;
+  const int tid = threadIdx.x, b = blockIdx.y, lane = tid & 63;
+  const int c = blockIdx.x / kBlocksPerChunk, p = (blockIdx.x % kBlocksPerChunk) * kRankThreads + tid;
+  const int n = g.t.n;
+  const unsigned long long* sorted = g.sorted + (long)b * g.nchunks * kSortCap;
+  const bool active = p < min(n - c * kSortCap, kSortCap);
+  bool finite = false;
+  if (active) {
+    const unsigned long long key = sorted[(long)c * kSortCap + p];
+    // cnt[o] = entries of chunk o to search (0: this key's own chunk, or past the last chunk); pos[o] = keys of chunk o known to
+    // be above `key`.  The searches of one step are independent loads: one round trip per step, not one per (step, chunk).
+    int cnt[kMaxChunks], pos[kMaxChunks];
+#pragma unroll
+    for (int o = 0; o < kMaxChunks; ++o) {
+      cnt[o] = (o == c || o >= g.nchunks) ? 0 : min(n - o * kSortCap, kSortCap);
+      pos[o] = 0;
+    }
+    for (int s = kSortCap; s > 0; s >>= 1) {
+      unsigned long long v[kMaxChunks];
+#pragma unroll
+      for (int o = 0; o < kMaxChunks; ++o) {
+        const int t = pos[o] + s;
+        v[o] = t <= cnt[o] ? sorted[(long)o * kSortCap + t - 1] : 0ull;
+      }
+#pragma unroll
+      for (int o = 0; o < kMaxChunks; ++o)
+        if (pos[o] + s <= cnt[o] && v[o] > key) pos[o] += s;
+    }
+    int rank = p;
+#pragma unroll
+    for (int o = 0; o < kMaxChunks; ++o) rank += pos[o];
+    if (rank < g.t.K) {
+      const int idx = (int)(key & 0xffffu);
+      const float s = g.t.scores[(long)b * n + idx];
+      const float4 bx = *(const float4*)(g.t.boxes + ((long)b * n + idx) * 4);
+      float* o = g.t.out_boxes + ((long)b * g.t.K + rank) * 5;
+      o[0] = bx.x; o[1] = bx.y; o[2] = bx.z; o[3] = bx.w; o[4] = s;
+      g.t.out_index[(long)b * g.t.K + rank] = idx;
+      finite = s > -INFINITY;
+    }
+  }
+  const unsigned long long fm = __ballot(finite);
+  if (lane == 0 && fm) atomicAdd(&g.t.out_count[b], __popcll(fm));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -480,6 +565,29 @@ extern "C" int relnet_topk_sort(const float* scores, const float* boxes, float* 
   if (n <= 32 * kSortThreads) topk_sort_kernel<32><<<B, kSortThreads, 0, (hipStream_t)stream>>>(g);
   else topk_sort_kernel<64><<<B, kSortThreads, 0, (hipStream_t)stream>>>(g);
   return check_launch("relnet_topk_sort");
+}
+
+// The same outputs for any 0 < K <= n < 65536 (K <= kSortCap included: the same bits as relnet_topk_sort), through a workspace
+// of relnet_topk_sort_large_workspace_bytes(B, n) bytes that needs no initialisation and is free again when the launches have run.
+extern "C" long relnet_topk_sort_large_workspace_bytes(int B, int n) {
+  if (B <= 0 || n <= 0 || n >= 65536) return -1;
+  return (long)B * ((n + kSortCap - 1) / kSortCap) * kSortCap * (long)sizeof(unsigned long long);
+}
+
+extern "C" int relnet_topk_sort_large(const float* scores, const float* boxes, float* out_boxes5, int* out_index, int* out_count,
+                                      int B, int n, int K, void* workspace, long workspace_bytes, void* stream) {
+  RELNET_REQUIRE(scores && boxes && out_boxes5 && out_index && out_count, "relnet_topk_sort_large: null operand");
+  RELNET_REQUIRE(B > 0 && n > 0 && n < 65536 && K > 0 && K <= n, "relnet_topk_sort_large: need 0 < K <= n < 65536 (n=%d K=%d)", n, K);
+  const long need = relnet_topk_sort_large_workspace_bytes(B, n);
+  RELNET_REQUIRE(workspace && ((unsigned long long)workspace & 7ull) == 0 && workspace_bytes >= need,
+                 "relnet_topk_sort_large: workspace must be 8-byte aligned and hold relnet_topk_sort_large_workspace_bytes(B, n) = %ld bytes (got %ld)",
+                 need, workspace ? workspace_bytes : 0l);
+  const int nchunks = (n + kSortCap - 1) / kSortCap;
+  TopkLargeArgs g{TopkArgs{scores, boxes, out_boxes5, out_index, out_count, n, K}, (unsigned long long*)workspace, nchunks};
+  topk_chunk_sort_kernel<<<dim3(nchunks, B), kSortThreads, 0, (hipStream_t)stream>>>(g);
+  if (check_launch("relnet_topk_sort_large (chunk sort)") != 0) return -1;
+  topk_rank_gather_kernel<<<dim3(nchunks * (kSortCap / kRankThreads), B), kRankThreads, 0, (hipStream_t)stream>>>(g);
+  return check_launch("relnet_topk_sort_large (rank)");
 }
 
 extern "C" int relnet_nms_mask(const float* boxes5, const int* counts, unsigned long long* mask,

@@ -125,13 +125,29 @@ def _pred_eval_device(detector, test_data, imdb, logger, device):
     return info, stats, all_boxes
 
 
-def generate_proposals(detector, test_data, imdb, thresh=0.0, device='cuda', save=True, device_recall=False):
+def _proposal_values(cfg, proposal_settings):
+    """(pre_nms_top_n, post_nms_top_n, nms_thresh, min_size) handed to propose_batch: the detector's rpn_* values, or with
+    proposal_settings the proposal_* ones (TEST.PROPOSAL_*; ValueError naming the first that is not set)."""
+    if not proposal_settings:
+        return cfg.rpn_pre_nms_top_n, cfg.rpn_post_nms_top_n, cfg.rpn_nms_thresh, cfg.rpn_min_size
+    names = ('proposal_pre_nms_top_n', 'proposal_post_nms_top_n', 'proposal_nms_thresh', 'proposal_min_size')
+    for name in names:
+        if getattr(cfg, name, None) is None:
+            raise ValueError("proposal_settings=True needs cfg.%s (TEST.%s; Config.from_experiment fills it)" % (name, name.upper()))
+    return tuple(getattr(cfg, name) for name in names)
+
+
+def generate_proposals(detector, test_data, imdb, thresh=0.0, device='cuda', save=True, device_recall=False, proposal_settings=False):
     """tester.py:63-126: per image [n,5] = (x1,y1,x2,y2 at the ORIGINAL scale, rpn score); returns the list and writes
     `<rpn_path>/rpn_data/<name>_rpn.pkl` (+ `_full_rpn.pkl` when thresh > 0).
     device_recall=True: returns (list, DeviceRecall) -- every batch's rois are scored on the device as they come (scaled and
-    thresholded there as below, no copy to the host) and copied to the host once at the end; the list is the same."""
+    thresholded there as below, no copy to the host) and copied to the host once at the end; the list is the same.
+    proposal_settings=True: the proposals are cut with cfg.proposal_* (TEST.PROPOSAL_PRE_NMS_TOP_N 20000 -> PROPOSAL_POST_NMS_TOP_N 2000,
+    the values the reference's tester.py:78-79 symbol is built with and the rcnn_fpn_* experiments are defined on) instead of the
+    detector's cfg.rpn_* (6000 -> 300); ValueError before any device work if one of the four is None."""
+    pre, post, nms_thresh, min_size = _proposal_values(detector.cfg, proposal_settings)
     if device_recall:
-        return _generate_proposals_device(detector, test_data, imdb, thresh, device, save)
+        return _generate_proposals_device(detector, test_data, imdb, thresh, device, save, proposal_settings=proposal_settings)
     from ..operator_py.proposal import propose_batch
     imdb_boxes, original = [None] * imdb.num_images, [None] * imdb.num_images
     c = detector.cfg
@@ -140,7 +156,7 @@ def generate_proposals(detector, test_data, imdb, thresh=0.0, device='cuda', sav
             data, im_info = batch['data'].to(device), batch['im_info'].to(device)
             f = detector.backbone.forward(data)
             rois, scores = propose_batch(f['rpn_cls_score'].float(), f['rpn_bbox_pred'].float(), im_info, detector.anchors,
-                                         c.feat_stride, c.rpn_pre_nms_top_n, c.rpn_post_nms_top_n, c.rpn_nms_thresh, c.rpn_min_size,
+                                         c.feat_stride, pre, post, nms_thresh, min_size,
                                          im_hw=(int(data.shape[2]), int(data.shape[3])), softmax_pairs=True)
             for b, idx in enumerate(batch['index']):
                 boxes = rois[b, :, 1:].cpu().numpy() / float(batch['im_info'][b, 2])
@@ -155,25 +171,27 @@ def generate_proposals(detector, test_data, imdb, thresh=0.0, device='cuda', sav
     return imdb_boxes
 
 
-def _rpn_batch(detector, batch, device):
+def _rpn_batch(detector, batch, device, proposal_settings=False):
     from ..operator_py.proposal import propose_batch
     c = detector.cfg
+    pre, post, nms_thresh, min_size = _proposal_values(c, proposal_settings)
     data, im_info = batch['data'].to(device), batch['im_info'].to(device)
     f = detector.backbone.forward(data)
     return propose_batch(f['rpn_cls_score'].float(), f['rpn_bbox_pred'].float(), im_info, detector.anchors, c.feat_stride,
-                         c.rpn_pre_nms_top_n, c.rpn_post_nms_top_n, c.rpn_nms_thresh, c.rpn_min_size,
+                         pre, post, nms_thresh, min_size,
                          im_hw=(int(data.shape[2]), int(data.shape[3])), softmax_pairs=True), im_info
 
 
-def _generate_proposals_device(detector, test_data, imdb, thresh, device, save):
+def _generate_proposals_device(detector, test_data, imdb, thresh, device, save, proposal_settings=False):
     """generate_proposals(device_recall=True): the proposal list is built from one device-to-host copy of every batch's rois
-    and scores with the default path's numpy expressions, so it is identical to it."""
+    and scores with the default path's numpy expressions, so it is identical to it.  proposal_settings: as generate_proposals."""
     from .device_recall import DeviceRecall
+    _proposal_values(detector.cfg, proposal_settings)          # (refuse unset values before the evaluator touches the device)
     ev = DeviceRecall(imdb, device=device)
     kept = []
     with torch.no_grad():
         for batch in test_data:
-            (rois, scores), im_info = _rpn_batch(detector, batch, device)
+            (rois, scores), im_info = _rpn_batch(detector, batch, device, proposal_settings)
             scores = scores.reshape(rois.shape[0], rois.shape[1])
             ev.add(rois[:, :, 1:], None, batch['index'], scores=scores, thresh=thresh, scale=im_info[:, 2])
             kept.append((list(batch['index']), [float(batch['im_info'][b, 2]) for b in range(len(batch['index']))],
@@ -200,18 +218,19 @@ def _generate_proposals_device(detector, test_data, imdb, thresh, device, save):
     return imdb_boxes, ev
 
 
-def test_rpn(detector, test_data, imdb, thresh=0.0, device='cuda', device_eval=False, logger=None):
+def test_rpn(detector, test_data, imdb, thresh=0.0, device='cuda', device_eval=False, logger=None, proposal_settings=False):
     """function/test_rpn.py:25-76: proposals of every test image (generate_proposals, which writes `<name>_rpn.pkl`) scored by
     imdb.evaluate_recall against imdb.gt_roidb(); returns all_log_info.  device_eval=True scores them on the device
     (DeviceRecall) and returns the same string.
     The reference builds its network with sym.get_symbol_rpn, which none of its shipped symbol files defines; the RPN here is
     the detector's backbone RPN head + propose_batch, as generate_proposals uses it.  `test_data` is a non-shuffled
-    TestLoader(imdb.gt_roidb(), cfg, has_rpn=True)."""
+    TestLoader(imdb.gt_roidb(), cfg, has_rpn=True).  proposal_settings: as generate_proposals (TEST.PROPOSAL_*, 20000 -> 2000)."""
     if device_eval:
-        _, ev = generate_proposals(detector, test_data, imdb, thresh=thresh, device=device, device_recall=True)
+        _, ev = generate_proposals(detector, test_data, imdb, thresh=thresh, device=device, device_recall=True,
+                                   proposal_settings=proposal_settings)
         all_log_info = ev.summarize()[0]
     else:
-        imdb_boxes = generate_proposals(detector, test_data, imdb, thresh=thresh, device=device)
+        imdb_boxes = generate_proposals(detector, test_data, imdb, thresh=thresh, device=device, proposal_settings=proposal_settings)
         all_log_info = imdb.evaluate_recall(imdb.gt_roidb(), candidate_boxes=imdb_boxes)
     if logger:
         logger.info(all_log_info)

@@ -27,6 +27,12 @@ class Config(object):
     rpn_post_nms_top_n = 300
     rpn_nms_thresh = 0.7
     rpn_min_size = 0
+    # TEST.PROPOSAL_*: how the experiment files word proposal GENERATION (tester.generate_proposals / test_rpn with proposal_settings=True;
+    # 20000 -> 2000 at 0.7 in every shipped file), as opposed to the detector's own RPN_* above.  None = not set: from_experiment fills them
+    proposal_pre_nms_top_n = None
+    proposal_post_nms_top_n = None
+    proposal_nms_thresh = None
+    proposal_min_size = None
     num_classes = 81
     nms = 0.6                 # TEST.NMS (sigma for soft-NMS, IoU threshold for NMS)
     softnms = True            # TEST.SOFTNMS
@@ -68,6 +74,8 @@ class Config(object):
         src = t if train else te
         c.rpn_pre_nms_top_n, c.rpn_post_nms_top_n = src.RPN_PRE_NMS_TOP_N, src.RPN_POST_NMS_TOP_N
         c.rpn_nms_thresh, c.rpn_min_size = src.RPN_NMS_THRESH, src.RPN_MIN_SIZE
+        c.proposal_pre_nms_top_n, c.proposal_post_nms_top_n = te.PROPOSAL_PRE_NMS_TOP_N, te.PROPOSAL_POST_NMS_TOP_N
+        c.proposal_nms_thresh, c.proposal_min_size = te.PROPOSAL_NMS_THRESH, te.PROPOSAL_MIN_SIZE
         c.nms, c.softnms, c.max_per_image = te.NMS, te.SOFTNMS, te.max_per_image
         c.learn_nms = bool(t.LEARN_NMS if train else te.LEARN_NMS)
         c.first_n = (t.FIRST_N if train else te.FIRST_N) or cls.first_n

@@ -45,6 +45,8 @@ _SIGNATURES = {
     'relnet_bottleneck_chain_s2': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'relnet_proposal_decode': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'relnet_topk_sort': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'relnet_topk_sort_large_workspace_bytes': (C.c_long, [_i, _i]),
+    'relnet_topk_sort_large': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _l, _vp]),
     'relnet_nms_mask': (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     'relnet_nms_scan': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     '_nms': (None, [_vp, _vp, _vp, _i, _i, _f, _i]),

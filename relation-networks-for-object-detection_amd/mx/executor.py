@@ -510,6 +510,8 @@ class Executor(object):
             fn = F.max_pool2d if a_str(a, 'pool_type', 'max') == 'max' else F.avg_pool2d
             return fn(x.float(), k, s, p, ceil_mode=full)
         if n.op == 'Custom':
+            # (the CustomOp protocol as it is: op_type='proposal' with rpn_pre_nms_top_n='20000', rpn_post_nms_top_n='2000' runs here unchanged,
+            # operator_py/proposal.py routes the sort past 8192 candidates to relnet_topk_sort_large)
             prop = R.custom_prop(a)
             in_data = [x.float().contiguous() for x in ins]
             shapes = prop.infer_shape([tuple(x.shape) for x in in_data])

@@ -47,7 +47,10 @@ def propose_batch(cls_prob, bbox_pred, im_info, anchors, feat_stride, pre_nms_to
     """Batched proposal: cls_prob [B,2A,H,W], bbox_pred [B,4A,H,W], im_info [B,3] ->
     rois [B, post, 5] (column 0 = image index in the batch), scores [B, post] (want_num: + num_keep [B] int32, the
     number of boxes that survived NMS before padding: where it is < post the reference pads with `npr.choice` (random,
-    proposal.py:154-156) and this operator with keep[i mod num_keep] -- a documented, unavoidable difference)."""
+    proposal.py:154-156) and this operator with keep[i mod num_keep] -- a documented, unavoidable difference).
+    Any pre_nms_top_n works while the grid has fewer than 65536 anchors: up to 8192 candidates ops.topk_sort is one LDS sort, above it
+    (TEST.PROPOSAL_PRE_NMS_TOP_N 20000, TRAIN.RPN_PRE_NMS_TOP_N 12000) relnet_topk_sort_large; post_nms_top_n <= 2048 (PROPOSAL_POST_NMS_TOP_N
+    2000 included) takes the fused greedy NMS, larger values the mask + scan pair."""
     boxes, scores = ops.proposal_decode(cls_prob, bbox_pred, im_info, anchors, feat_stride, min_size,
                                         im_hw=im_hw, softmax_pairs=softmax_pairs)
     n = scores.shape[1]
@@ -102,6 +105,9 @@ class ProposalOperator(CustomOp):
 
 @register("proposal")
 class ProposalProp(CustomOpProp):
+    """The attributes are the reference's strings.  rpn_pre_nms_top_n='20000', rpn_post_nms_top_n='2000' (the experiment files'
+    TEST.PROPOSAL_* values) work as they are: propose_batch routes the sort past 8192 candidates to relnet_topk_sort_large."""
+
     def __init__(self, feat_stride='16', scales='(8, 16, 32)', ratios='(0.5, 1, 2)', output_score='False',
                  rpn_pre_nms_top_n='6000', rpn_post_nms_top_n='300', threshold='0.3', rpn_min_size='16'):
         super(ProposalProp, self).__init__(need_top_grad=False)

@@ -283,15 +283,37 @@ def proposal_decode(cls_prob, bbox_deltas, im_info, base_anchors, feat_stride=16
 
 
 def topk_sort(scores, boxes, K):
-    """Descending top-K: -> det [B,K,5] (x1,y1,x2,y2,score), index [B,K] int32, count [B]."""
+    """Descending top-K: -> det [B,K,5] (x1,y1,x2,y2,score), index [B,K] int32, count [B].
+    min(K, n) <= TOPK_LDS_CAP: relnet_topk_sort (one workgroup per image); above it relnet_topk_sort_large (topk_sort_large)."""
+    _chk(scores, boxes)
+    B, n = scores.shape
+    K = min(K, n)
+    if K > TOPK_LDS_CAP:
+        return topk_sort_large(scores, boxes, K)
+    det = torch.empty((B, K, 5), device=scores.device, dtype=torch.float32)
+    index = torch.empty((B, K), device=scores.device, dtype=torch.int32)
+    count = torch.empty((B,), device=scores.device, dtype=torch.int32)
+    _lib.call('relnet_topk_sort', scores.data_ptr(), boxes.data_ptr(), det.data_ptr(), index.data_ptr(),
+              count.data_ptr(), B, n, K, _stream())
+    return det, index, count
+
+
+TOPK_LDS_CAP = 8192      # kSortCap of csrc/proposal.hip: the most keys relnet_topk_sort sorts
+
+
+def topk_sort_large(scores, boxes, K):
+    """topk_sort through relnet_topk_sort_large for any 0 < K <= n < 65536 (TEST.PROPOSAL_PRE_NMS_TOP_N 20000): chunk sorts in LDS
+    + rank by counting, the same order and outputs; the workspace is a torch.empty of relnet_topk_sort_large_workspace_bytes."""
     _chk(scores, boxes)
     B, n = scores.shape
     K = min(K, n)
     det = torch.empty((B, K, 5), device=scores.device, dtype=torch.float32)
     index = torch.empty((B, K), device=scores.device, dtype=torch.int32)
     count = torch.empty((B,), device=scores.device, dtype=torch.int32)
-    _lib.call('relnet_topk_sort', scores.data_ptr(), boxes.data_ptr(), det.data_ptr(), index.data_ptr(),
-              count.data_ptr(), B, n, K, _stream())
+    nbytes = max(int(_lib.load().relnet_topk_sort_large_workspace_bytes(B, n)), 0)      # (-1: the entry below refuses the shape and says why)
+    ws = torch.empty((nbytes // 8,), device=scores.device, dtype=torch.int64)
+    _lib.call('relnet_topk_sort_large', scores.data_ptr(), boxes.data_ptr(), det.data_ptr(), index.data_ptr(),
+              count.data_ptr(), B, n, K, _ptr(ws) if nbytes else None, nbytes, _stream())
     return det, index, count
 
 
